@@ -2,6 +2,8 @@
 """bench.py -- Mray/s of the TriPlane ray-march hot path on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full    (+ roofline, CPU baseline and parity, the other presets / variants, bench_extras.json)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR    (+ the last timed step's rgb_map / depth_map as DIR/*.npy)
     python bench.py --gpus N --steps K --warmup W           (N > 1 without a launcher: starts its own N ranks, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
@@ -12,6 +14,8 @@ at N>1 the frame's rows are dealt out to the ranks in 10-row blocks (strong scal
 BASELINE.json's north_star asks) and every frame is followed by one RCCL all-gather of the composited pixels,
 double-buffered so that frame k's exchange overlaps frame k+1's march.
 Rays and parameters are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints the headline line; every other measurement or check
+(a statistics launch for the roofline, the CPU baseline, other presets / variants, the N > 1 exchange figures) runs with --full only.
 """
 from __future__ import annotations
 
@@ -163,22 +167,23 @@ FIXED_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_st
 
 
 def compact_line(result: dict) -> str:
-    """The ONE JSON line the driver parses (it keeps an ~8 KB tail of stdout): fixed keys, config, roofline (numbers only),
+    """The ONE JSON line the driver parses (it keeps an ~8 KB tail of stdout): fixed keys, config and, with --full, roofline (numbers only),
     cpu_baseline, parity, the multi-GPU figures -- never more than LINE_LIMIT bytes.  Everything else (extras, notes, the
     algorithmic D3 model) goes to bench_extras.json."""
     out = {k: result[k] for k in FIXED_KEYS}
     for k in ("value", "ms_per_step"):
         out[k] = _r(out[k], 6)
     out["config"] = result["config"]
-    rf = result.get("roofline") or {}
-    keep = ("bound", "achieved", "peak", "unit", "frac", "mfma_frac", "mfma_TFLOPs", "useful_op_frac", "traffic", "kernel", "kernel_ms", "flops_per_launch",
-            "valu_insts_necessary", "clock_ghz", "active_samples_per_ray", "evaluated_samples_per_ray", "mlp_passes", "binding")
-    crf = {k: _r(rf.get(k), 5) for k in keep if k in rf}
-    ph = rf.get("physical")
-    if ph:
-        crf["physical"] = _r({k: ph[k] for k in ("simd_busy", "mfma_busy", "valu_busy_raw", "mfma_issue_in_valu", "ta_busy", "l1_tag_frac", "l2_hit", "hbm_frac",
-                                               "pmc_stale", "source", "vgpr", "scratch_bytes_per_lane") if k in ph})
-    out["roofline"] = crf
+    if "roofline" in result:              # --full only
+        rf = result["roofline"]
+        keep = ("bound", "achieved", "peak", "unit", "frac", "mfma_frac", "mfma_TFLOPs", "useful_op_frac", "traffic", "kernel", "kernel_ms", "flops_per_launch",
+                "valu_insts_necessary", "clock_ghz", "active_samples_per_ray", "evaluated_samples_per_ray", "mlp_passes", "binding")
+        crf = {k: _r(rf.get(k), 5) for k in keep if k in rf}
+        ph = rf.get("physical")
+        if ph:
+            crf["physical"] = _r({k: ph[k] for k in ("simd_busy", "mfma_busy", "valu_busy_raw", "mfma_issue_in_valu", "ta_busy", "l1_tag_frac", "l2_hit", "hbm_frac",
+                                                   "pmc_stale", "source", "vgpr", "scratch_bytes_per_lane") if k in ph})
+        out["roofline"] = crf
     if "cpu_baseline" in result:
         cb = result["cpu_baseline"]
         out["cpu_baseline"] = {"value": _r(cb["value"], 5), "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"], "sample": cb["sample"][:160]}
@@ -222,6 +227,22 @@ def write_side_file(result: dict):
                     json.dump(full, fh, indent=1)
             except OSError:
                 pass
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (the inputs are seeded, so two builds of the project can be compared output
+    for output); at most DUMP_LIMIT_BYTES in all."""
+    host = {k: np.ascontiguousarray((v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float32))
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def plan_tiles(n, wide, resident):
@@ -416,10 +437,17 @@ def main():
                     "default of ngf_amd.triplane.TriPlane since round 3; 0 = level 1")
     ap.add_argument("--bake-color", type=int, default=1, help="1 = NGF_F_BAKE_COLOR (layer 1 pre-composed into 64-channel colour planes): optimisation level 3, the "
                     "default of ngf_amd.triplane.TriPlane since round 4; 0 = level 2")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="N=1 only: also time the other presets / variants (untimed region)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full only: budget of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--extras", type=int, default=1, help="--full at N=1 only: also time the other presets / variants (untimed region)")
     ap.add_argument("--knobs", default="", help="experiments only: comma-separated ngf_debug_set knobs, e.g. waves=12,tile_w=8,kernel=1")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, also measure and check everything else: roofline (statistics launch, "
+                    "PMC summaries), CPU baseline and parity (--cpu-seconds), the other presets / variants (--extras), at N > 1 the serial shard "
+                    "launches, the exchange alone, the critical path and the gathered frame against a single-GPU render; writes bench_extras.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rgb_map, depth_map of the whole "
+                    "frame in image order) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps {args.steps} --warmup {args.warmup}: at least one timed step, no negative warm-up")
 
     if args.gpus < 1 or (args.gpus > 1 and H % (args.gpus * 10) != 0):
         raise SystemExit(f"--gpus {args.gpus}: the frame's 800 rows are dealt out in 10-row blocks, so N must divide 80 (1, 2, 4, 5, 8, 10, 16 ...)")
@@ -542,87 +570,11 @@ def main():
     elapsed = time_steps(step_fn, args.steps, args.warmup, device, dist_on, finish, None if dist_on else marks, preamble=render_only)
     ms_step = elapsed / args.steps * 1e3
     value = n_total * args.steps / elapsed / 1e6
-    # per-step launch durations of the TIMED loop (HIP events on the launch stream around every render launch); at N > 1 the frames of the timed
-    # loop overlap on two render streams, so the shard's launch is timed afterwards: the same K launches one after the other on one stream
     if dist_on:
         pipe.drain()
-        torch.cuda.synchronize(device)
-        marks = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-        for a, b in marks:
-            a.record()
-            f(rays, N_samples=S, white_bg=True, out=(pipe.send[0][1], pipe.send[0][2]), **kw)
-            b.record()
-        torch.cuda.synchronize(device)
-    launch_ms = np.array([a.elapsed_time(b) for a, b in marks], np.float64)
-    launch_stats = {"min": float(launch_ms.min()), "median": float(np.median(launch_ms)), "max": float(launch_ms.max())}
-
-    # dominant kernel: its duration = the median of the timed loop's own launches; algorithmic bytes from the measured active count
-    k_ms = launch_stats["median"]
-    f(rays, N_samples=S, white_bg=True, collect_stats=True, **kw)
-    torch.cuda.synchronize(device)
-    st = f.last_stats.cpu().numpy().astype(np.float64)
-    s_active = st[1] / n_local
-    bytes_launch = alg_bytes_per_ray(s_active, model) * n_local
-    achieved = bytes_launch / (k_ms * 1e-3) / 1e9
-    # Executed matrix work of the launch: passes x MFMAs per 16-sample pass x 2*16*16*4 flop (v_mfma_f32_16x16x4_f32);
-    # agrees with rocprofv3's SQ_INSTS_VALU_MFMA_MOPS_F32 x 512 (profiles/r01_pmc_*.txt).
-    # (144 feature + 64 layer-2 MFMAs per pass, or 64 with the baked colour planes; the 16 view-input MFMAs are spent once per
-    # 8-ray tile since the per-ray view fold)
-    mfma_per_pass = 64 if args.bake_color else 208
-    n_tiles = plan_tiles(n_local, 8, torch.cuda.get_device_properties(device).multi_processor_count * 12)      # launch_render's tile plan (csrc/ngf_field.hip)
-    mfma_flops = (st[2] * mfma_per_pass + n_tiles * 16) * 2048.0 if model == "triplane" else None
-    # rocprofv3 --pmc summary of THIS workload (profiles/collect.sh -> profiles/r02_<workload>_pmc.json); flagged stale when the
-    # library it was collected with is not the one loaded now
-    tag = f"{model}_{args.preset}" + ("_bd" if args.bake_density and not args.bake_color else "") + ("_bdc" if args.bake_color else "")
-    pmc = load_pmc(tag)
-    if mfma_flops is None and pmc is not None:
-        # InfoInv runs its density MLP on the matrix pipe inside the march, so the executed flops are not a function of the pass
-        # count alone: take SQ_INSTS_VALU_MFMA_MOPS_F32 x 512 of the PMC run of this very workload
-        mfma_flops = pmc.get("mfma_flops_per_dispatch")
-    alg = {"unit": "GB/s", "achieved": achieved, "peak": HBM_PEAK_GBS, "frac_of_hbm_peak": achieved / HBM_PEAK_GBS, "bytes_per_launch": bytes_launch,
-           "flops_per_launch": (S * 550.0 + s_active * 71400.0) * n_local if model == "triplane" else None}
-    if mfma_flops is not None:
-        tf = mfma_flops / (k_ms * 1e-3) / 1e12
-        roofline = {"bound": "mfma", "achieved": tf, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s", "frac": tf / MFMA_F32_PEAK_TF,
-                    "traffic": None if pmc is None else pmc.get("hbm_traffic_bytes_per_launch", 0.0) * n_local / n_total,
-                    "flops_per_launch": mfma_flops}
-    else:
-        # no matrix work counted (e.g. InfoInv without a PMC summary): the physical HBM-side figure, or nothing -- never the model bytes
-        hb = None if pmc is None or "hbm_traffic_bytes_per_launch" not in pmc else pmc["hbm_traffic_bytes_per_launch"] * n_local / n_total
-        roofline = {"bound": "hbm", "achieved": None if hb is None else hb / (k_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": None if hb is None else hb / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": hb}
-    roofline["physical"] = physical_roofs(pmc, k_ms, n_local / n_total)
-    ph = roofline["physical"]
-    if mfma_flops is not None:
-        roofline.update({"mfma_frac": roofline["frac"], "mfma_TFLOPs": roofline["achieved"]})
-    if model == "triplane" and args.bake_color and mfma_flops is not None:
-        # What binds these launches is the SIMD's fp32 datapath: on gfx950 a SIMD executes its MFMA and its VALU instructions one after the
-        # other (profiles/r02_micro_mfma_valu_overlap.txt), so `bound` names that roof.  `frac` is WORK / TIME / PEAK of THIS run (round 6,
-        # VERDICT r5 item 7): work = the launch's executed fp32 matrix flops (pass and tile counts of this run's statistics launch) + its
-        # NECESSARY vector arithmetic (NECESSARY_VALU x this run's march iterations, passes and tiles; one wave64 instruction = 64 lanes x one
-        # FMA = 128 flop, i.e. 2 SIMD cycles at the peak rate of 64 flop/clk/SIMD -- the same price list as the matrix instruction's 32 cycles),
-        # time = the median launch of the timed loop, peak = 157.3 TFLOP/s (1024 SIMDs x 64 flop/clk x 2.4 GHz).  The counters' busy fractions
-        # (MFMA busy + VALU busy - MFMA issue: utilisation, not work) stay under `physical`, from the committed PMC run.
-        need = (st[0] / 64.0) * NECESSARY_VALU["march_iteration"] + st[2] * NECESSARY_VALU["shade_pass"] + n_tiles * NECESSARY_VALU["per_tile"]
-        work = mfma_flops + VALU_FLOP_PER_WAVE_INST * need
-        tf_simd = work / (k_ms * 1e-3) / 1e12
-        roofline.update({"bound": "simd", "achieved": tf_simd, "frac": tf_simd / MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
-                         "valu_insts_necessary": need, "clock_ghz": PEAK_CLOCK_GHZ,
-                         "prices": {"mfma_16x16x4_f32_cycles": 32, "wave64_valu_cycles": 2, "flop_per_wave64_valu": VALU_FLOP_PER_WAVE_INST, "simds": 1024}})
-        roofline["binding"] = ("simd fp32 datapath (MFMA + VALU share it): frac = (executed MFMA flops + 128 x necessary wave64 VALU instructions) / "
-                               "kernel_ms / 157.3 TFLOP/s, all from this run; counter busy fractions under physical")
-        if ph is not None and pmc.get("valu_insts_per_launch"):
-            mfma_cyc = mfma_flops / 64.0                                   # 64 fp32 flops per SIMD cycle
-            issued = (pmc["valu_insts_per_launch"] - pmc.get("mfma_flops_per_dispatch", 0.0) / 2048.0) * n_local / n_total
-            roofline["useful_op_frac"] = (4.0 * need + mfma_cyc) / (4.0 * issued + mfma_cyc)
-            roofline["valu_insts_issued"] = issued
-    # SURVEY 8 D3's model against both peaks (both exceed 1 at level 3 -- the kernel does not do D3's work: folds (i)-(iii)
-    # and exact early termination remove it, with green parity -- so D3 is a model, not a roof of this kernel)
-    alg["frac_of_mfma_peak"] = None if alg["flops_per_launch"] is None else alg["flops_per_launch"] / (k_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TF
-    alg["note"] = "both fractions exceed 1 at levels 1-3 by construction: cache-resident taps counted as HBM bytes, pre-composed layers counted as flops"
-    roofline.update({"kernel": "ngf::render_kernel", "kernel_ms": k_ms, "active_samples_per_ray": s_active,
-                     "evaluated_samples_per_ray": st[0] / n_local,      # in-box samples the march evaluated (exact early termination skips the rest)
-                      "mlp_passes": st[2], "algorithmic_d3": alg})
+    if args.dump_outputs and rank == 0:
+        # what the timed path handed its caller in the last timed step: the frame's rgb_map / depth_map (at N > 1 the gathered frame in image order)
+        dump_outputs(args.dump_outputs, dict(zip(("rgb_map", "depth_map"), last_frame[0] if dist_on else (rgb_view, depth_view))))
 
     result = {
         "metric": "Mray/sec (800x800 lego-style frame, 192 samples/ray)", "value": value, "unit": "Mray/s", "n_gpus": world,
@@ -635,10 +587,6 @@ def main():
                              "1-channel planes, per-ray view fold)" if args.bake_color else "2 (layer 1 o basis, per-ray view fold, density_decoder folded into "
                              "1-channel planes)" if args.bake_density else "1 (layer 1 o basis, per-ray view fold)") if model == "triplane" else "default",
                    "bake_density": int(args.bake_density), "bake_color": int(args.bake_color)},
-        "roofline": roofline,
-        # per-step durations of the render launch inside the timed loop (HIP events): SURVEY 8 D1 asks for the median of >= 20 frames
-        "ms_per_step_median": launch_stats["median"], "launch_ms": launch_stats,
-        "value_from_median_launch": n_local / launch_stats["median"] / 1e3,
     }
     result["config"]["clock_preamble"] = {"launches": PREAMBLE_REPORT.get("launches"), "ms": _r(PREAMBLE_REPORT.get("ms", 0.0), 3),
                                           "what": "untimed render launches between the W warm-up steps and the timed region (GPU clocks ramp 25-30 ms after idle)"}
@@ -647,14 +595,99 @@ def main():
         result["config"]["hip_hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES", "4 (runtime default)")
     if BACKEND != "nccl" or ONE_DEVICE:
         result["config"]["test_backend"] = f"{BACKEND}, {'all ranks on one GPU' if ONE_DEVICE else 'one GPU per rank'}: a test of the N > 1 path, not a measurement"
-    if dist_on:
-        result["launch_ms_note"] = ("N > 1: the timed loop's frames overlap on two render streams; launch_ms / roofline.kernel_ms are the same K shard launches "
-                                    "run one after the other on one stream after the timed region")
     if args.knobs:
         result["config"]["knobs"] = args.knobs
     result["config"]["launcher"] = "self (bench.py started its own torch.distributed.run)" if self_launched else ("torch.distributed.run" if "WORLD_SIZE" in os.environ else "none (single process)")
+    if args.full or not dist_on:
+        # per-step launch durations of the TIMED loop (HIP events on the launch stream around every render launch); at N > 1 the frames of the timed
+        # loop overlap on two render streams, so the shard's launch is timed afterwards (--full only): the same K launches one after the other on one stream
+        if dist_on:
+            torch.cuda.synchronize(device)
+            marks = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+            for a, b in marks:
+                a.record()
+                f(rays, N_samples=S, white_bg=True, out=(pipe.send[0][1], pipe.send[0][2]), **kw)
+                b.record()
+            torch.cuda.synchronize(device)
+            result["launch_ms_note"] = ("N > 1: the timed loop's frames overlap on two render streams; launch_ms / roofline.kernel_ms are the same K shard launches "
+                                        "run one after the other on one stream after the timed region")
+        launch_ms = np.array([a.elapsed_time(b) for a, b in marks], np.float64)
+        launch_stats = {"min": float(launch_ms.min()), "median": float(np.median(launch_ms)), "max": float(launch_ms.max())}
+        # per-step durations of the render launch inside the timed loop (HIP events): SURVEY 8 D1 asks for the median of >= 20 frames
+        result.update({"ms_per_step_median": launch_stats["median"], "launch_ms": launch_stats,
+                       "value_from_median_launch": n_local / launch_stats["median"] / 1e3})
 
-    if dist_on:
+    if args.full:
+        # dominant kernel: its duration = the median of the timed loop's own launches; algorithmic bytes from the measured active count
+        k_ms = launch_stats["median"]
+        f(rays, N_samples=S, white_bg=True, collect_stats=True, **kw)
+        torch.cuda.synchronize(device)
+        st = f.last_stats.cpu().numpy().astype(np.float64)
+        s_active = st[1] / n_local
+        bytes_launch = alg_bytes_per_ray(s_active, model) * n_local
+        achieved = bytes_launch / (k_ms * 1e-3) / 1e9
+        # Executed matrix work of the launch: passes x MFMAs per 16-sample pass x 2*16*16*4 flop (v_mfma_f32_16x16x4_f32);
+        # agrees with rocprofv3's SQ_INSTS_VALU_MFMA_MOPS_F32 x 512 (profiles/r01_pmc_*.txt).
+        # (144 feature + 64 layer-2 MFMAs per pass, or 64 with the baked colour planes; the 16 view-input MFMAs are spent once per
+        # 8-ray tile since the per-ray view fold)
+        mfma_per_pass = 64 if args.bake_color else 208
+        n_tiles = plan_tiles(n_local, 8, torch.cuda.get_device_properties(device).multi_processor_count * 12)      # launch_render's tile plan (csrc/ngf_field.hip)
+        mfma_flops = (st[2] * mfma_per_pass + n_tiles * 16) * 2048.0 if model == "triplane" else None
+        # rocprofv3 --pmc summary of THIS workload (profiles/collect.sh -> profiles/r02_<workload>_pmc.json); flagged stale when the
+        # library it was collected with is not the one loaded now
+        tag = f"{model}_{args.preset}" + ("_bd" if args.bake_density and not args.bake_color else "") + ("_bdc" if args.bake_color else "")
+        pmc = load_pmc(tag)
+        if mfma_flops is None and pmc is not None:
+            # InfoInv runs its density MLP on the matrix pipe inside the march, so the executed flops are not a function of the pass
+            # count alone: take SQ_INSTS_VALU_MFMA_MOPS_F32 x 512 of the PMC run of this very workload
+            mfma_flops = pmc.get("mfma_flops_per_dispatch")
+        alg = {"unit": "GB/s", "achieved": achieved, "peak": HBM_PEAK_GBS, "frac_of_hbm_peak": achieved / HBM_PEAK_GBS, "bytes_per_launch": bytes_launch,
+               "flops_per_launch": (S * 550.0 + s_active * 71400.0) * n_local if model == "triplane" else None}
+        if mfma_flops is not None:
+            tf = mfma_flops / (k_ms * 1e-3) / 1e12
+            roofline = {"bound": "mfma", "achieved": tf, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s", "frac": tf / MFMA_F32_PEAK_TF,
+                        "traffic": None if pmc is None else pmc.get("hbm_traffic_bytes_per_launch", 0.0) * n_local / n_total,
+                        "flops_per_launch": mfma_flops}
+        else:
+            # no matrix work counted (e.g. InfoInv without a PMC summary): the physical HBM-side figure, or nothing -- never the model bytes
+            hb = None if pmc is None or "hbm_traffic_bytes_per_launch" not in pmc else pmc["hbm_traffic_bytes_per_launch"] * n_local / n_total
+            roofline = {"bound": "hbm", "achieved": None if hb is None else hb / (k_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": None if hb is None else hb / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": hb}
+        roofline["physical"] = physical_roofs(pmc, k_ms, n_local / n_total)
+        ph = roofline["physical"]
+        if mfma_flops is not None:
+            roofline.update({"mfma_frac": roofline["frac"], "mfma_TFLOPs": roofline["achieved"]})
+        if model == "triplane" and args.bake_color and mfma_flops is not None:
+            # What binds these launches is the SIMD's fp32 datapath: on gfx950 a SIMD executes its MFMA and its VALU instructions one after the
+            # other (profiles/r02_micro_mfma_valu_overlap.txt), so `bound` names that roof.  `frac` is WORK / TIME / PEAK of THIS run (round 6,
+            # VERDICT r5 item 7): work = the launch's executed fp32 matrix flops (pass and tile counts of this run's statistics launch) + its
+            # NECESSARY vector arithmetic (NECESSARY_VALU x this run's march iterations, passes and tiles; one wave64 instruction = 64 lanes x one
+            # FMA = 128 flop, i.e. 2 SIMD cycles at the peak rate of 64 flop/clk/SIMD -- the same price list as the matrix instruction's 32 cycles),
+            # time = the median launch of the timed loop, peak = 157.3 TFLOP/s (1024 SIMDs x 64 flop/clk x 2.4 GHz).  The counters' busy fractions
+            # (MFMA busy + VALU busy - MFMA issue: utilisation, not work) stay under `physical`, from the committed PMC run.
+            need = (st[0] / 64.0) * NECESSARY_VALU["march_iteration"] + st[2] * NECESSARY_VALU["shade_pass"] + n_tiles * NECESSARY_VALU["per_tile"]
+            work = mfma_flops + VALU_FLOP_PER_WAVE_INST * need
+            tf_simd = work / (k_ms * 1e-3) / 1e12
+            roofline.update({"bound": "simd", "achieved": tf_simd, "frac": tf_simd / MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
+                             "valu_insts_necessary": need, "clock_ghz": PEAK_CLOCK_GHZ,
+                             "prices": {"mfma_16x16x4_f32_cycles": 32, "wave64_valu_cycles": 2, "flop_per_wave64_valu": VALU_FLOP_PER_WAVE_INST, "simds": 1024}})
+            roofline["binding"] = ("simd fp32 datapath (MFMA + VALU share it): frac = (executed MFMA flops + 128 x necessary wave64 VALU instructions) / "
+                                   "kernel_ms / 157.3 TFLOP/s, all from this run; counter busy fractions under physical")
+            if ph is not None and pmc.get("valu_insts_per_launch"):
+                mfma_cyc = mfma_flops / 64.0                                   # 64 fp32 flops per SIMD cycle
+                issued = (pmc["valu_insts_per_launch"] - pmc.get("mfma_flops_per_dispatch", 0.0) / 2048.0) * n_local / n_total
+                roofline["useful_op_frac"] = (4.0 * need + mfma_cyc) / (4.0 * issued + mfma_cyc)
+                roofline["valu_insts_issued"] = issued
+        # SURVEY 8 D3's model against both peaks (both exceed 1 at level 3 -- the kernel does not do D3's work: folds (i)-(iii)
+        # and exact early termination remove it, with green parity -- so D3 is a model, not a roof of this kernel)
+        alg["frac_of_mfma_peak"] = None if alg["flops_per_launch"] is None else alg["flops_per_launch"] / (k_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TF
+        alg["note"] = "both fractions exceed 1 at levels 1-3 by construction: cache-resident taps counted as HBM bytes, pre-composed layers counted as flops"
+        roofline.update({"kernel": "ngf::render_kernel", "kernel_ms": k_ms, "active_samples_per_ray": s_active,
+                         "evaluated_samples_per_ray": st[0] / n_local,      # in-box samples the march evaluated (exact early termination skips the rest)
+                          "mlp_passes": st[2], "algorithmic_d3": alg})
+        result["roofline"] = roofline
+
+    if args.full and dist_on:
         # untimed: the gathered, re-ordered frame of the last step against a direct render of the whole frame on this rank
         whole = torch.from_numpy(synth.lookat_rays(H, W)).to(device)
         ref = f(whole, N_samples=S, white_bg=True, **kw)
@@ -699,7 +732,7 @@ def main():
         result["critical_path_ms"] = {"render": float(cpm[0]), "all_gather": float(cpm[1]), "reorder": float(cpm[2]),
                                       "sum": float(cpm.sum()), "note": "unpipelined, max over ranks"}
 
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         if args.cpu_seconds > 0:
             cb, par = cpu_baseline(params, g, step, rays_np, args.cpu_seconds, f, kw)
             result["cpu_baseline"] = cb
@@ -1084,7 +1117,8 @@ def main():
         except Exception:
             pass
         sys.stdout.flush()
-        write_side_file(result)
+        if args.full:
+            write_side_file(result)
         print(compact_line(result), flush=True)
 
 

@@ -90,6 +90,45 @@ def test_side_file_keeps_everything(monkeypatch, tmp_path):
     assert full["roofline"]["algorithmic_d3"]["bytes_per_launch"] == res["roofline"]["algorithmic_d3"]["bytes_per_launch"]
 
 
+def test_plain_line_is_the_headline_alone(monkeypatch):
+    """A run without --full has no roofline, CPU baseline, extras or multi-GPU figures: its line is the fixed keys, config and the timed loop's own
+    per-step launch times, and nothing refers to a side file."""
+    res = _fat_result(monkeypatch)
+    for k in ("roofline", "cpu_baseline", "parity", "speedup_vs_cpu_port", "gathered_frame_bit_identical_to_single_gpu_render", "all_gather_ms",
+              "all_gather_bytes_per_rank", "shard_kernel_ms", "critical_path_ms", "extras", "value_from_median_launch"):
+        res.pop(k)
+    d = json.loads(bench.compact_line(res))
+    assert set(d) == set(bench.FIXED_KEYS) | {"config", "ms_per_step_median", "launch_ms"}
+    assert d["ms_per_step"] == pytest.approx(res["ms_per_step"], rel=1e-5) and d["launch_ms"]["median"] == pytest.approx(res["ms_per_step_median"], rel=1e-4)
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per array, float32, the values unchanged; more than the limit in all is refused before anything is written."""
+    import numpy as np
+    import torch
+    rgb = np.random.default_rng(1).random((1000, 3), dtype=np.float32)
+    depth = np.linspace(2.0, 6.0, 1000)
+    bench.dump_outputs(str(tmp_path / "out"), {"rgb_map": torch.from_numpy(rgb), "depth_map": depth})
+    got_rgb, got_depth = np.load(tmp_path / "out" / "rgb_map.npy"), np.load(tmp_path / "out" / "depth_map.npy")
+    assert got_rgb.dtype == np.float32 and np.array_equal(got_rgb, rgb)
+    assert got_depth.dtype == np.float32 and np.array_equal(got_depth, depth.astype(np.float32))
+    assert 640000 * 4 * 4 <= bench.DUMP_LIMIT_BYTES <= 64 << 20           # the 800x800 frame's rgb + depth fit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 12000 + 4000 - 1)       # float32 rgb + depth: 16000 bytes
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"rgb_map": rgb, "depth_map": depth})
+    assert not (tmp_path / "big").exists()
+
+
+def test_bench_options_and_step_count_check():
+    """--full and --dump-outputs are options of the command line; --steps must name at least one timed step (checked before any device is looked for)."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps 0" in r.stderr
+
+
 @pytest.mark.parametrize("n", [2, 4, 8])
 def test_self_launch_command_line(n):
     """`python bench.py --gpus N` without a launcher starts its own N ranks -- the command line is the driver's own
