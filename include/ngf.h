@@ -313,6 +313,54 @@ int ngf_train_params_changed(ngf_trainer *t);
  * scatter calls that took the per-tap path (10).  This reads and clears them (out16: 16 x uint64, host).  Synchronises. */
 int ngf_train_debug_sections(ngf_trainer *t, uint64_t *out16);
 
+/* ---- the InfoInv tree's training step: InfoInv/main.py:262-330 -------------------------------------------------------------------
+ * Replaces field(rays_train, is_train=True, infoinv=...) (InfoInv/models/FieldBase.py:228-282) under autograd and its backward, for a
+ * caller that owns the loss and the optimiser (ngf_amd.infoinv.TriPlane with `differentiable = True`).  Additive to ABI 5; the TriPlane
+ * trainer above is unchanged.  The parameters stay caller-owned device tensors in the REFERENCE layouts and are only read; the trainer owns
+ * channel-last plane copies, the per-sample buffers of the largest batch (about 4 KB per (ray, sample) pair: ngf_infoinv_trainer_bytes())
+ * and the gradients of its last backward.
+ * Parameter indices (`which`): 0-2 plane_xy/yz/xz [1,96,H,W] (H, W per plane, >= 2), 3/4 density_decoder.mlp.0 weight [32,72] / bias,
+ * 5/6 mlp.2 [32,32] / [32], 7/8 mlp.4 [1,32] / [1], 9 rgb_decoder.basis.weight [216,216], 10/11 rgb_decoder.mlp.0 [64,231] / [64],
+ * 12/13 mlp.2 [64,64] / [64], 14/15 mlp.4 [3,64] / [3]. */
+#define NGF_INFOINV_TRAIN_PARAMS 16
+typedef struct ngf_infoinv_train_desc {
+    float aabb[6];
+    float near_, far_, step, distance_scale, weight_thres;
+    float *plane[3];
+    int32_t plane_h[3], plane_w[3];
+    float *dens_w1, *dens_b1, *dens_w2, *dens_b2, *dens_w3, *dens_b3;
+    float *basis, *w1, *b1, *w2, *b2, *w3, *b3;
+    const uint8_t *mask_bits;      /* optional alpha mask, the packbits image of the field descriptor (copied at create); NULL = none */
+    int32_t mask_d, mask_h, mask_w;
+    float mask_aabb[6];
+    int64_t max_rays;              /* largest batch */
+    int32_t max_samples;           /* largest N_samples; max_rays * max_samples < 2^31 */
+} ngf_infoinv_train_desc;
+typedef struct ngf_infoinv_trainer ngf_infoinv_trainer;
+/* create waits for hip_stream once (the mask copy); destroy calls hipFree (which waits for the device). */
+int ngf_infoinv_trainer_create(const ngf_infoinv_train_desc *desc, ngf_infoinv_trainer **out, void *hip_stream);
+int ngf_infoinv_trainer_destroy(ngf_infoinv_trainer *t);
+int64_t ngf_infoinv_trainer_bytes(const ngf_infoinv_trainer *t);
+int32_t ngf_sizeof_infoinv_train_desc(void);
+/* The training-mode forward: sample_ray with jitter [n] (the per-ray U[0,1) of FieldBase.py:129; NULL = 0), the alpha mask, the density MLP,
+ * raw2alpha, the colour MLP on the samples with weight > weight_thres, compositing; white_bg = `white_bg or coin` of FieldBase.py:270, infoinv =
+ * the reference's flag (PE modulation of the plane features on / off).  Writes rgb_map [n,3] (after the clamp) and depth_map [n] (carries no
+ * gradient); *ticket (HOST) names this forward.  Asynchronous on hip_stream (the active count stays on the device).  Between this call and its
+ * backward `rays`, `jitter` and the parameter tensors must stay alive and unchanged.  The planes are re-packed at the first forward and after
+ * ngf_infoinv_train_params_changed; the MLP weights are read at every forward.
+ * The backward takes d loss / d rgb_map [n,3] (DEVICE) of the forward named by `ticket` and leaves the gradients of all 16 parameters in the
+ * trainer; a ticket that is not the trainer's last forward returns NGF_E_STALE (run the forward again).  It may run more than once per
+ * forward, and gives bit-identical gradients each time: the plane gradients are summed in 64-bit fixed point (scale chosen on the device
+ * so that no sum overflows), the weight gradients over fixed row chunks in fp64.  Asynchronous on hip_stream.
+ * get_grads copies every wanted gradient of the last backward into out[k] (DEVICE, reference layout; NULL = skip); NGF_E_ARG if no backward
+ * ran since the last forward.  A trainer must not be used from two streams at once. */
+int ngf_infoinv_train_forward(ngf_infoinv_trainer *t, const float *rays, const float *jitter, int64_t n, int32_t n_samples, int32_t white_bg,
+                              int32_t infoinv, float *rgb_map, float *depth_map, int64_t *ticket, void *hip_stream);
+int ngf_infoinv_train_backward_grad(ngf_infoinv_trainer *t, int64_t ticket, const float *d_rgb_map, void *hip_stream);
+int ngf_infoinv_train_get_grads(ngf_infoinv_trainer *t, float *const out[NGF_INFOINV_TRAIN_PARAMS], void *hip_stream);
+/* after writing to a plane's memory (optimizer.step(), checkpoint load, in-place edit): the next forward re-packs the planes */
+int ngf_infoinv_train_params_changed(ngf_infoinv_trainer *t);
+
 /* ---- UV-Mapping (NeuTex) colour path: UV-Mapping/model/model.py:27-59 ----------------------------------------
  * 29 nn.Linear layers in evaluation order, reference layouts (weight [out,in], bias [out], float32, device):
  *   [0..11]  net_geometry_decoder.block.{0,2,..,22}   63-256, 10x 256-256, 256-1          (decoder.py:201-237)

@@ -1,0 +1,298 @@
+// ngf_infoinv_train.hip -- the C ABI of the InfoInv trainer (include/ngf.h: ngf_infoinv_trainer_*, ngf_infoinv_train_*); kernels in
+// ngf_infoinv_train.hpp.  A translation unit of its own: ngf_field.hip and the ISA lint's compile of it stay as they were.
+#include "ngf_host.hpp"
+#include "ngf_infoinv_train.hpp"
+
+using namespace ngf;
+
+struct ngf_infoinv_trainer {
+    int device = -1;
+    ngf_infoinv_train_desc desc{};
+    int64_t max_rays = 0;
+    int32_t max_samples = 0;
+    int64_t cap = 0;                                   // max_rays * max_samples
+    std::vector<void *> allocs;
+    int64_t bytes = 0;
+    float *tex[3] = {nullptr, nullptr, nullptr};       // packed planes
+    unsigned long long *gacc[3] = {nullptr, nullptr, nullptr};
+    uint8_t *mask = nullptr;
+    float *dw1t = nullptr, *cw1t = nullptr;
+    IiArgs A{};                                        // buffers of the last forward
+    double *part = nullptr;                            // GEMM chunk partials
+    int64_t part_elems = 0;
+    double *m64 = nullptr;                             // [64][231] colour M in fp64
+    float *grads[NGF_INFOINV_TRAIN_PARAMS] = {};       // gradients of the last backward, reference layouts
+    int64_t grad_elems[NGF_INFOINV_TRAIN_PARAMS] = {};
+    bool packed = false;
+    int64_t ticket = 0;                                // last forward's ticket (0 = none)
+    bool have_grads = false;
+};
+
+namespace {
+
+int ii_alloc(ngf_infoinv_trainer *t, void **p, size_t bytes)
+{
+    *p = nullptr;
+    if (bytes == 0) bytes = 16;
+    HIP_TRY(hipMalloc(p, bytes));
+    t->allocs.push_back(*p);
+    t->bytes += (int64_t)bytes;
+    return NGF_OK;
+}
+
+template <typename T>
+int ii_alloc_n(ngf_infoinv_trainer *t, T **p, size_t n)
+{
+    void *v = nullptr;
+    int rc = ii_alloc(t, &v, n * sizeof(T));
+    *p = (T *)v;
+    return rc;
+}
+
+void ii_free(ngf_infoinv_trainer *t)
+{
+    for (void *p : t->allocs) (void)hipFree(p);
+    t->allocs.clear();
+}
+
+// the parameter tensors in `which` order (include/ngf.h) and their element counts
+void ii_params(const ngf_infoinv_train_desc &d, const float *p[NGF_INFOINV_TRAIN_PARAMS], int64_t n[NGF_INFOINV_TRAIN_PARAMS])
+{
+    const float *ps[NGF_INFOINV_TRAIN_PARAMS] = {d.plane[0], d.plane[1], d.plane[2], d.dens_w1, d.dens_b1, d.dens_w2, d.dens_b2, d.dens_w3, d.dens_b3,
+                                                 d.basis, d.w1, d.b1, d.w2, d.b2, d.w3, d.b3};
+    const int64_t ns[NGF_INFOINV_TRAIN_PARAMS] = {(int64_t)kIiC * d.plane_h[0] * d.plane_w[0], (int64_t)kIiC * d.plane_h[1] * d.plane_w[1],
+                                                  (int64_t)kIiC * d.plane_h[2] * d.plane_w[2], kIiDH * kIiDIn, kIiDH, kIiDH * kIiDH, kIiDH, kIiDH, 1,
+                                                  kIiCF * kIiCF, kIiCH * kIiCIn, kIiCH, kIiCH * kIiCH, kIiCH, 3 * kIiCH, 3};
+    for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k) { p[k] = ps[k]; n[k] = ns[k]; }
+}
+
+unsigned grid_for(int64_t work, int block = 256, int64_t cap = 1 << 16)
+{
+    int64_t g = (work + block - 1) / block;
+    if (g < 1) g = 1;
+    return (unsigned)(g < cap ? g : cap);
+}
+
+// one weight-gradient GEMM (X: M delta rows, Y: N input rows, both [k][cap]) -> gw [M][N], gb [M] (nullable), gw64 (nullable)
+int ii_xty(ngf_infoinv_trainer *t, const float *X, const float *Y, int64_t rows_cap, const int32_t *rows_dev, int M, int N, float *gw, float *gb,
+           double *gw64, hipStream_t st)
+{
+    IiXty G{};
+    G.X = X; G.Y = Y; G.ld = t->cap; G.rows = rows_cap; G.rows_dev = rows_dev; G.M = M; G.N = N; G.NB = N + 1; G.part = t->part;
+    const int chunks = (int)((rows_cap + kIiChunk - 1) / kIiChunk);
+    const int tiles = ((M + 31) / 32) * ((N + 1 + 31) / 32);
+    if ((int64_t)chunks * M * (N + 1) > t->part_elems) return fail(NGF_E_ARG, "ngf_infoinv: GEMM partials do not fit (internal)");
+    hipLaunchKernelGGL(ii_xty_kernel, dim3(chunks > 0 ? chunks : 1, tiles), dim3(256), 0, st, G);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_xty_reduce_kernel, dim3((M * (N + 1) + 255) / 256), dim3(256), 0, st, (const double *)t->part, chunks > 0 ? chunks : 1, M, N,
+                       gw, gb, gw64);
+    HIP_TRY(hipGetLastError());
+    return NGF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t ngf_sizeof_infoinv_train_desc(void) { return (int32_t)sizeof(ngf_infoinv_train_desc); }
+
+int64_t ngf_infoinv_trainer_bytes(const ngf_infoinv_trainer *t) { return t ? t->bytes : 0; }
+
+int ngf_infoinv_trainer_destroy(ngf_infoinv_trainer *t)
+{
+    if (!t) return NGF_OK;
+    {
+        DeviceScope ds(t->device);
+        ii_free(t);
+    }
+    delete t;
+    return NGF_OK;
+}
+
+int ngf_infoinv_trainer_create(const ngf_infoinv_train_desc *desc, ngf_infoinv_trainer **out, void *hip_stream)
+{
+    if (!desc || !out) return fail(NGF_E_ARG, "ngf_infoinv_trainer_create: null argument");
+    *out = nullptr;
+    const ngf_infoinv_train_desc &d = *desc;
+    if (d.max_rays <= 0 || d.max_samples <= 0) return fail(NGF_E_ARG, "ngf_infoinv_trainer_create: max_rays and max_samples must be > 0");
+    const float *ps[NGF_INFOINV_TRAIN_PARAMS];
+    int64_t ns[NGF_INFOINV_TRAIN_PARAMS];
+    ii_params(d, ps, ns);
+    for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k)
+        if (!ps[k]) return fail(NGF_E_ARG, "ngf_infoinv_trainer_create: parameter %d is NULL", k);
+    for (int p = 0; p < 3; ++p)
+        if (d.plane_h[p] < 2 || d.plane_w[p] < 2 || (int64_t)(d.plane_h[p] + 2) * (d.plane_w[p] + 2) * kIiC >= (1ll << 31))
+            return fail(NGF_E_ARG, "ngf_infoinv_trainer_create: plane %d has an unsupported size %d x %d", p, d.plane_h[p], d.plane_w[p]);
+    const int64_t cap = d.max_rays * (int64_t)d.max_samples;
+    if (cap >= (1ll << 31)) return fail(NGF_E_ARG, "ngf_infoinv_trainer_create: max_rays * max_samples must be < 2^31");
+    if (d.mask_bits && (d.mask_d < 1 || d.mask_h < 1 || d.mask_w < 1)) return fail(NGF_E_ARG, "ngf_infoinv_trainer_create: bad mask size");
+    hipStream_t st = (hipStream_t)hip_stream;
+    ngf_infoinv_trainer *t = new (std::nothrow) ngf_infoinv_trainer();
+    if (!t) return fail(NGF_E_HIP, "ngf_infoinv_trainer_create: out of host memory");
+    HIP_TRY(hipGetDevice(&t->device));
+    t->desc = d;
+    t->max_rays = d.max_rays;
+    t->max_samples = d.max_samples;
+    t->cap = cap;
+    IiArgs &A = t->A;
+    int rc = 0;
+    auto bail = [&](int r) { ii_free(t); delete t; return r; };
+    for (int p = 0; p < 3; ++p) {
+        const int64_t tex = (int64_t)(d.plane_h[p] + 2) * (d.plane_w[p] + 2);
+        if ((rc = ii_alloc_n(t, &t->tex[p], tex * kIiC)) || (rc = ii_alloc_n(t, &t->gacc[p], tex * kIiC))) return bail(rc);
+        Tex &x = A.tex[p];
+        x.p = t->tex[p]; x.W = d.plane_w[p]; x.H = d.plane_h[p]; x.stride = d.plane_w[p] + 2;
+        x.fw = (float)(d.plane_w[p] - 1); x.fh = (float)(d.plane_h[p] - 1);
+        A.gacc[p] = t->gacc[p];
+    }
+    if (d.mask_bits) {
+        const size_t mb = ((size_t)d.mask_d * d.mask_h * d.mask_w + 7) / 8;
+        if ((rc = ii_alloc_n(t, &t->mask, mb))) return bail(rc);
+        if (hipMemcpyAsync(t->mask, d.mask_bits, mb, hipMemcpyDeviceToDevice, st) != hipSuccess) return bail(fail(NGF_E_HIP, "mask copy failed"));
+    }
+    if ((rc = ii_alloc_n(t, &t->dw1t, kIiDIn * kIiDH)) || (rc = ii_alloc_n(t, &t->cw1t, kIiCIn * kIiCH))) return bail(rc);
+    const int64_t nr = d.max_rays;
+    A.cap = cap;
+    if ((rc = ii_alloc_n(t, &A.et, cap)) || (rc = ii_alloc_n(t, &A.sg, cap)) || (rc = ii_alloc_n(t, &A.w, cap)) || (rc = ii_alloc_n(t, &A.tb, cap)) ||
+        (rc = ii_alloc_n(t, &A.dxs, cap)) || (rc = ii_alloc_n(t, &A.xn, 3 * cap)) || (rc = ii_alloc_n(t, &A.valid, cap)) ||
+        (rc = ii_alloc_n(t, &A.d_in, kIiDIn * cap)) || (rc = ii_alloc_n(t, &A.d_h1, kIiDH * cap)) || (rc = ii_alloc_n(t, &A.d_h2, kIiDH * cap)) ||
+        (rc = ii_alloc_n(t, &A.d_d1, kIiDH * cap)) || (rc = ii_alloc_n(t, &A.d_d2, kIiDH * cap)) || (rc = ii_alloc_n(t, &A.d_g, kIiDIn * cap)) ||
+        (rc = ii_alloc_n(t, &A.count, nr)) || (rc = ii_alloc_n(t, &A.offset, nr + 1)) || (rc = ii_alloc_n(t, &A.list, cap)) ||
+        (rc = ii_alloc_n(t, &A.c_in, kIiCIn * cap)) || (rc = ii_alloc_n(t, &A.c_h1, kIiCH * cap)) || (rc = ii_alloc_n(t, &A.c_h2, kIiCH * cap)) ||
+        (rc = ii_alloc_n(t, &A.c_rgb, 3 * cap)) || (rc = ii_alloc_n(t, &A.c_d1, kIiCH * cap)) || (rc = ii_alloc_n(t, &A.c_d2, kIiCH * cap)) ||
+        (rc = ii_alloc_n(t, &A.c_d3, 3 * cap)) || (rc = ii_alloc_n(t, &A.c_g, kIiCF * cap)) || (rc = ii_alloc_n(t, &A.pre, 3 * nr)) ||
+        (rc = ii_alloc_n(t, &A.bound, kIiBoundBlocks + 1)) || (rc = ii_alloc_n(t, &t->m64, kIiCH * kIiCIn)))
+        return bail(rc);
+    const int64_t chunks = (cap + kIiChunk - 1) / kIiChunk;
+    t->part_elems = chunks * kIiCH * (kIiCIn + 1);
+    if ((rc = ii_alloc_n(t, &t->part, t->part_elems))) return bail(rc);
+    for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k) {
+        t->grad_elems[k] = ns[k];
+        if ((rc = ii_alloc_n(t, &t->grads[k], ns[k]))) return bail(rc);
+    }
+    // the geometry of the desc
+    for (int k = 0; k < 3; ++k) {
+        A.a0[k] = d.aabb[k]; A.a1[k] = d.aabb[3 + k];
+        A.inv[k] = 2.0f / (d.aabb[3 + k] - d.aabb[k]);                 // invaabbSize = 2 / aabbSize (FieldBase.py:66)
+        if (d.mask_bits) { A.m_a0[k] = d.mask_aabb[k]; A.m_inv[k] = 1.0f / (d.mask_aabb[3 + k] - d.mask_aabb[k]) * 2.0f; }
+    }
+    A.near_ = d.near_; A.far_ = d.far_; A.step = d.step; A.dscale = d.distance_scale; A.thr = d.weight_thres;
+    A.mask_bits = t->mask; A.mD = d.mask_d; A.mH = d.mask_h; A.mW = d.mask_w;
+    A.dw1 = d.dens_w1; A.db1 = d.dens_b1; A.dw2 = d.dens_w2; A.db2 = d.dens_b2; A.dw3 = d.dens_w3; A.db3 = d.dens_b3;
+    A.basis = d.basis; A.w1 = d.w1; A.b1 = d.b1; A.w2 = d.w2; A.b2 = d.b2; A.w3 = d.w3; A.b3 = d.b3;
+    A.dw1t = t->dw1t; A.cw1t = t->cw1t;
+    if (hipStreamSynchronize(st) != hipSuccess) return bail(fail(NGF_E_HIP, "ngf_infoinv_trainer_create: stream synchronisation failed"));
+    *out = t;
+    return NGF_OK;
+}
+
+int ngf_infoinv_train_params_changed(ngf_infoinv_trainer *t)
+{
+    if (!t) return fail(NGF_E_ARG, "ngf_infoinv_train_params_changed: null trainer");
+    t->packed = false;
+    return NGF_OK;
+}
+
+int ngf_infoinv_train_forward(ngf_infoinv_trainer *t, const float *rays, const float *jitter, int64_t n, int32_t n_samples, int32_t white_bg,
+                              int32_t infoinv, float *rgb_map, float *depth_map, int64_t *ticket, void *hip_stream)
+{
+    if (!t || !rays || !rgb_map || !depth_map || !ticket) return fail(NGF_E_ARG, "ngf_infoinv_train_forward: null argument");
+    if (n <= 0 || n > t->max_rays || n_samples <= 0 || n_samples > t->max_samples)
+        return fail(NGF_E_ARG, "ngf_infoinv_train_forward: n = %lld, n_samples = %d outside the trainer's 1..%lld x 1..%d", (long long)n, n_samples,
+                    (long long)t->max_rays, t->max_samples);
+    hipStream_t st = (hipStream_t)hip_stream;
+    IiArgs &A = t->A;
+    t->ticket = 0;                         // the buffers are overwritten from here on: no earlier ticket stays valid, even if this call fails
+    t->have_grads = false;
+    A.rays = rays; A.jitter = jitter; A.n = n; A.S = n_samples; A.white_bg = white_bg ? 1 : 0; A.infoinv = infoinv ? 1 : 0;
+    A.rgb_out = rgb_map; A.depth_out = depth_map; A.d_rgb = nullptr;
+    if (!t->packed) {
+        for (int p = 0; p < 3; ++p) {
+            hipLaunchKernelGGL(ii_pack_kernel, dim3(grid_for((int64_t)(A.tex[p].H + 2) * (A.tex[p].W + 2) * kIiC)), dim3(256), 0, st,
+                               (const float *)t->desc.plane[p], A.tex[p].H, A.tex[p].W, t->tex[p]);
+            HIP_TRY(hipGetLastError());
+        }
+        t->packed = true;
+    }
+    hipLaunchKernelGGL(ii_prep_kernel, dim3((kIiCIn * kIiCH + 255) / 256), dim3(256), 0, st, A, t->dw1t, t->cw1t);
+    HIP_TRY(hipGetLastError());
+    const int64_t pairs = n * (int64_t)n_samples;
+    hipLaunchKernelGGL(ii_density_fwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    const unsigned rg = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(ii_scan_kernel, dim3(rg), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_prefix_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)A.count, n, A.offset);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_list_kernel, dim3(rg), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_color_fwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);       // the active count is read on the device
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_composite_fwd_kernel, dim3(rg), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    static int64_t next_ticket = 0;
+    t->ticket = __atomic_add_fetch(&next_ticket, 1, __ATOMIC_RELAXED);
+    *ticket = t->ticket;
+    return NGF_OK;
+}
+
+int ngf_infoinv_train_backward_grad(ngf_infoinv_trainer *t, int64_t ticket, const float *d_rgb_map, void *hip_stream)
+{
+    if (!t || !d_rgb_map) return fail(NGF_E_ARG, "ngf_infoinv_train_backward_grad: null argument");
+    if (ticket == 0 || ticket != t->ticket)
+        return fail(NGF_E_STALE, "ngf_infoinv_train_backward_grad: ticket %lld is not the trainer's last forward", (long long)ticket);
+    hipStream_t st = (hipStream_t)hip_stream;
+    IiArgs &A = t->A;
+    A.d_rgb = d_rgb_map;
+    const int64_t n = A.n, pairs = n * (int64_t)A.S;
+    const unsigned rg = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(ii_composite_bwd_kernel, dim3(rg), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_color_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_density_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    // plane gradients: bound -> scale -> fixed-point scatter -> reference layout
+    hipLaunchKernelGGL(ii_bound_kernel, dim3(kIiBoundBlocks), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_scale_kernel, dim3(1), dim3(64), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    for (int p = 0; p < 3; ++p)
+        HIP_TRY(hipMemsetAsync(t->gacc[p], 0, (size_t)(A.tex[p].H + 2) * (A.tex[p].W + 2) * kIiC * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(ii_scatter_kernel<true>, dim3(grid_for(pairs * kIiDIn)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_scatter_kernel<false>, dim3(grid_for(pairs * kIiCF)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    for (int p = 0; p < 3; ++p) {
+        hipLaunchKernelGGL(ii_plane_grad_kernel, dim3(grid_for((int64_t)kIiC * A.tex[p].H * A.tex[p].W)), dim3(256), 0, st,
+                           (const unsigned long long *)t->gacc[p], (const double *)A.bound, A.tex[p].H, A.tex[p].W, t->grads[p]);
+        HIP_TRY(hipGetLastError());
+    }
+    // weight gradients (which: 3..8 density mlp.{0,2,4}.{weight,bias}, 9 basis, 10..15 rgb mlp.{0,2,4}.{weight,bias})
+    int rc;
+    const int32_t *na = A.offset + n;
+    if ((rc = ii_xty(t, A.d_d1, A.d_in, pairs, nullptr, kIiDH, kIiDIn, t->grads[3], t->grads[4], nullptr, st)) ||
+        (rc = ii_xty(t, A.d_d2, A.d_h1, pairs, nullptr, kIiDH, kIiDH, t->grads[5], t->grads[6], nullptr, st)) ||
+        (rc = ii_xty(t, A.dxs, A.d_h2, pairs, nullptr, 1, kIiDH, t->grads[7], t->grads[8], nullptr, st)) ||
+        (rc = ii_xty(t, A.c_d1, A.c_in, pairs, na, kIiCH, kIiCIn, nullptr, t->grads[11], t->m64, st)) ||
+        (rc = ii_xty(t, A.c_d2, A.c_h1, pairs, na, kIiCH, kIiCH, t->grads[12], t->grads[13], nullptr, st)) ||
+        (rc = ii_xty(t, A.c_d3, A.c_h2, pairs, na, 3, kIiCH, t->grads[14], t->grads[15], nullptr, st)))
+        return rc;
+    hipLaunchKernelGGL(ii_unfold_kernel, dim3((kIiCF * kIiCF + 255) / 256), dim3(256), 0, st, (const double *)t->m64, A.basis, A.w1, t->grads[10],
+                       t->grads[9]);
+    HIP_TRY(hipGetLastError());
+    t->have_grads = true;
+    return NGF_OK;
+}
+
+int ngf_infoinv_train_get_grads(ngf_infoinv_trainer *t, float *const out[NGF_INFOINV_TRAIN_PARAMS], void *hip_stream)
+{
+    if (!t || !out) return fail(NGF_E_ARG, "ngf_infoinv_train_get_grads: null argument");
+    if (!t->have_grads) return fail(NGF_E_ARG, "ngf_infoinv_train_get_grads: no backward since the last forward");
+    hipStream_t st = (hipStream_t)hip_stream;
+    for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k)
+        if (out[k]) HIP_TRY(hipMemcpyAsync(out[k], t->grads[k], (size_t)t->grad_elems[k] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return NGF_OK;
+}
+
+}  // extern "C"

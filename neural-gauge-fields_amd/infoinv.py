@@ -1,11 +1,13 @@
 """``TriPlane`` of the InfoInv tree (InfoInv/models/Field.py:10-89): no gauge, 96-channel planes,
-plane features modulated by a sinusoidal encoding of the position, density MLP 72-32-32-1."""
+plane features modulated by a sinusoidal encoding of the position, density MLP 72-32-32-1.  With ``field.differentiable = True`` a
+training-mode forward under autograd is differentiable (ngf_amd.infoinv_train): the InfoInv tree's own loop (InfoInv/main.py:262-330) runs on it."""
 from __future__ import annotations
 
 import torch
 
 from . import _lib
 from .fieldbase import AlphaGridMask, Base, density_decoder, renderer, rgb_decoder  # noqa: F401
+from .triplane import _DensityL1
 
 
 class TriPlane(Base):
@@ -16,6 +18,9 @@ class TriPlane(Base):
     def __init__(self, aabb, gridSize, device, **kargs):
         kargs.pop('gauge_start', None)
         super().__init__(aabb, gridSize, device, **kargs)
+        # Opt-in switch of the differentiable training-mode forward (not a constructor argument: save() keeps the reference's kwargs).  False
+        # keeps the NotImplementedError of a forward that autograd would record.
+        self.differentiable = False
 
     def init_model(self, res=256, dim=96, scale=0.1, device=None, gauge_start=0):
         for name in ('plane_xy', 'plane_yz', 'plane_xz'):
@@ -41,11 +46,72 @@ class TriPlane(Base):
         """compute_alpha / getDenseAlpha / updateAlphaMask(..., infoinv=True) of InfoInv/models/FieldBase.py:140,161,180."""
         return int(bool(infoinv))
 
+    def density_L1(self):
+        """InfoInv/models/Field.py:107-110: mean|plane_xy| + mean|plane_yz| + mean|plane_xz|, differentiable.  On the device ngf_planes_l1 /
+        ngf_planes_l1_backward (triplane._DensityL1, any plane size); anything else is the reference's torch expression."""
+        planes = (self.plane_xy, self.plane_yz, self.plane_xz)
+        if all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.data_ptr() % 16 == 0 and p.numel() > 0 for p in planes):
+            return _DensityL1.apply(*planes)
+        return torch.mean(torch.abs(self.plane_xy)) + torch.mean(torch.abs(self.plane_yz)) + torch.mean(torch.abs(self.plane_xz))
+
+    def _infoinv_grad_engine(self, n, S):
+        """The device trainer behind a differentiable forward (ngf_amd.infoinv_train.InfoInvGrad); rebuilt when the batch outgrows it or a
+        parameter tensor / the alpha mask / the geometry was replaced."""
+        from . import infoinv_train
+        eng = getattr(self, '_ii_engine', None)
+        params = infoinv_train.train_params(self)
+        if eng is not None and eng._h is not None and eng.fits(n, S, params):
+            return eng
+        if eng is not None:
+            eng.release()
+            self._ii_engine = None
+        eng = infoinv_train.InfoInvGrad(self, max(int(n), getattr(eng, 'max_rays', 0)), max(int(S), getattr(eng, 'max_samples', 0)))
+        self._ii_engine = eng
+        return eng
+
+    def release_grad_engine(self):
+        """Free the differentiable forward's device buffers (about 3.5 KB per (ray, sample) pair of the largest batch seen, up to ~15 GB at the default
+        ``grad_max_pairs``); the next differentiable forward builds the engine again.  A pending backward of an earlier forward re-renders its batch."""
+        eng = getattr(self, '_ii_engine', None)
+        if eng is not None:
+            eng.release()
+            self._ii_engine = None
+
+    def _render_train_infoinv(self, rays_chunk, white_bg, N_samples, infoinv, jitter=None, coin=None):
+        """``forward(is_train=True)`` with gradients: the random draws of ``_render`` (jitter: torch.rand_like of sample_ray, FieldBase.py:128-130;
+        background coin: FieldBase.py:270), then one torch.autograd.Function over the sixteen parameters.  A batch of more than ``grad_max_pairs``
+        (ray, sample) pairs (default 2^22, ~16 GB of per-sample buffers) is cut into ray chunks, one autograd node each: the engine holds one chunk,
+        so the backward renders the other chunks again."""
+        from . import infoinv_train
+        dev = torch.device(self.device)
+        rays = rays_chunk.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError(f"rays_chunk must be [n,6], got {tuple(rays.shape)}")
+        n = rays.shape[0]
+        if n == 0:
+            raise ValueError("a differentiable forward needs at least one ray")
+        S = int(N_samples) if N_samples > 0 else int(self.nSamples)
+        jitter = torch.rand((n,), device=dev) if jitter is None else jitter.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
+        white = bool(white_bg or ((torch.rand((1,)) if coin is None else torch.tensor([float(coin)])) < 0.5))
+        cap = max(int(getattr(self, 'grad_max_pairs', 1 << 22)), S)
+        per = max(1, cap // S)
+        outs = []
+        for a in range(0, n, per):
+            r, j = rays[a:a + per], jitter[a:a + per]
+            eng = self._infoinv_grad_engine(r.shape[0], S)
+            outs.append(infoinv_train._InfoInvRender.apply(self, eng, r, j, S, white, bool(infoinv), *eng.params))
+        if len(outs) == 1:
+            return {'rgb_map': outs[0][0], 'depth_map': outs[0][1]}
+        return {'rgb_map': torch.cat([o[0] for o in outs], 0), 'depth_map': torch.cat([o[1] for o in outs], 0)}
+
     def forward(self, rays_chunk, white_bg=True, is_train=False, N_samples=-1, infoinv=True, collect_stats=False, out=None, jitter=None, coin=None, row_width=0):
-        """InfoInv/models/FieldBase.py:228.  Training the InfoInv tree is outside SURVEY.md section 8: a call that the
-        reference would record for autograd (is_train=True, grad enabled, parameters requiring gradients) raises instead of returning pixels
-        without a graph -- a loss built on them would otherwise only train its regularisers."""
+        """InfoInv/models/FieldBase.py:228.  A call that the reference would record for autograd (is_train=True, grad enabled, parameters
+        requiring gradients) returns a differentiable rgb_map when ``self.differentiable`` is set (the InfoInv training loop); without the switch
+        it raises instead of returning pixels without a graph -- a loss built on them would otherwise only train its regularisers."""
         if self._wants_grad(is_train):
-            raise NotImplementedError("ngf_amd.infoinv.TriPlane has no backward (InfoInv training is out of scope, DESIGN.md section 7): call it "
-                                      "under torch.no_grad() for a training-mode render, or train with the TriPlane tree")
+            if not getattr(self, 'differentiable', False):
+                raise NotImplementedError("ngf_amd.infoinv.TriPlane: a training-mode forward under autograd needs the opt-in "
+                                          "`field.differentiable = True` (the differentiable InfoInv forward, DESIGN.md section 4.6); or call it "
+                                          "under torch.no_grad() for a training-mode render")
+            return self._render_train_infoinv(rays_chunk, white_bg, N_samples, infoinv, jitter=jitter, coin=coin)
         return self._render(rays_chunk, white_bg, is_train, N_samples, mode=int(bool(infoinv)), collect_stats=collect_stats, out=out, jitter=jitter, coin=coin, row_width=row_width)
