@@ -432,6 +432,48 @@ int ngf_debug_xcd_histogram(unsigned *out8, int32_t workgroups, void *hip_stream
  * tiles.  Returns the number of segments (1..4); unused entries are zeroed.  (Why: a persistent grid ends when its last wave does -- narrow
  * tiles for the last rays let the waves run dry together.) */
 int ngf_debug_tile_plan(int64_t n, int32_t wide, int64_t resident, int32_t tail16, int64_t *seg_rays, int32_t *seg_shift);
+/* ---- the UV-Mapping (NeuTex) training step: UV-Mapping/model/model.py:27-59, 300-356 ---------------------------------------------------------
+ * Replaces NeuTex.forward under autograd (color, transmittance, uv, the blend weights, the sample positions) and its backward, for a caller that
+ * owns the losses and the optimiser (ngf_amd.uvmapping.NeuTex with `differentiable = True`).  Additive to ABI 5.  The 29 render layers are the
+ * ngf_uv_desc list above, caller-owned fp32 device tensors in the reference layouts, read in place at every launch.  The trainer owns the
+ * per-sample buffers of the largest batch (every layer's post-activation output: about 27 KB per (ray, sample) pair, ngf_uv_trainer_bytes())
+ * and the gradients of its last backward.
+ * Gradient slots (`out` of get_grads): 2 l = weight of layer l, 2 l + 1 = its bias, l in ngf_uv_desc order. */
+#define NGF_UV_TRAIN_PARAMS (2 * NGF_UV_LAYERS)
+typedef struct ngf_uv_train_desc {
+    int32_t sphere;
+    int32_t flags;                  /* must be 0: training is fp32 (no NGF_UV_F_SPLIT_BF16) */
+    const float *w[NGF_UV_LAYERS];
+    const float *b[NGF_UV_LAYERS];
+    int64_t max_rays;               /* largest n_cams * rays_per_cam */
+    int32_t max_samples;            /* largest n_samples; max_rays * max_samples * 296 < 2^31 */
+    int32_t pad_;
+} ngf_uv_train_desc;
+typedef struct ngf_uv_trainer ngf_uv_trainer;
+/* create allocates with hipMalloc; destroy calls hipFree (which waits for the device), as the InfoInv trainer does.  NeuTex keeps one trainer and
+ * grows it to the largest batch shape seen, so a training loop creates and destroys it once. */
+int ngf_uv_trainer_create(const ngf_uv_train_desc *desc, ngf_uv_trainer **out, void *hip_stream);
+int ngf_uv_trainer_destroy(ngf_uv_trainer *t);
+int64_t ngf_uv_trainer_bytes(const ngf_uv_trainer *t);
+int32_t ngf_sizeof_uv_train_desc(void);
+/* The training-mode forward of n_cams x rays_per_cam rays (campos [n_cams,3], raydir [n_cams,R,3], bg [n_cams,3] or NULL, jitter_u [n_cams,R,S]
+ * uniforms, all DEVICE): color [.,R,3] (tone mapped), trans [.,R] (background_blend_weight), uv [.,R,S,2|3] (the gauge output of every sample),
+ * weight [.,R,S] (blend_weight), ray_pos [.,R,S,3] (points_original).  *ticket (HOST) names this forward.  Asynchronous on hip_stream (the
+ * in-cube count stays on the device).  raydir, bg, ray_pos and the parameter tensors must stay alive and unchanged until its backward.
+ * The backward takes d loss / d color and d trans (DEVICE, required), d uv and d weight (NULL = zero) of the forward named by `ticket` and leaves
+ * the gradients of all 58 tensors in the trainer; a ticket that is not the trainer's last forward returns NGF_E_STALE (run the forward again).  It
+ * may run more than once per forward and gives bit-identical gradients each time: weight gradients are summed over fixed 1024-row chunks in
+ * chunk order, no float atomics.  get_grads copies every wanted gradient of the last backward into out[k] (DEVICE; NULL = skip); NGF_E_ARG if
+ * no backward ran since the last forward.  A trainer must not be used from two streams at once. */
+int ngf_uv_train_forward(ngf_uv_trainer *t, const float *campos, const float *raydir, const float *bg, const float *jitter_u, int32_t n_cams,
+                         int64_t rays_per_cam, int32_t n_samples, float *color, float *trans, float *uv, float *weight, float *ray_pos, int64_t *ticket,
+                         void *hip_stream);
+int ngf_uv_train_backward(ngf_uv_trainer *t, int64_t ticket, const float *d_color, const float *d_trans, const float *d_uv, const float *d_weight,
+                          void *hip_stream);
+int ngf_uv_train_get_grads(ngf_uv_trainer *t, float *const out[NGF_UV_TRAIN_PARAMS], void *hip_stream);
+/* after writing to a parameter's memory: kept for the trainers' common contract; the UV trainer packs nothing and reads the weights in place */
+int ngf_uv_train_params_changed(ngf_uv_trainer *t);
+
 /* test hook: the queue-position -> tile map of ngf_field_render_image evaluated on the host for `count` positions (RenderArgs::ord_*: ord_n positions
  * re-ordered, tpr tiles per image row, blocks of bw tiles x bh rows) */
 int ngf_debug_tile_order(const uint32_t *q, int64_t count, uint32_t ord_n, uint32_t tpr, uint32_t bw, uint32_t bh, uint32_t *out);

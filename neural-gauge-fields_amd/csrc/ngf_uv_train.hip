@@ -1,0 +1,366 @@
+// ngf_uv_train.hip -- the C ABI of the UV-Mapping (NeuTex) trainer (include/ngf.h: ngf_uv_trainer_*, ngf_uv_train_*); kernels in ngf_uv_train.hpp.
+// A translation unit of its own: ngf_uv.hip (the eval kernel, whose assembly tests/test_isa_lint.py lints) stays as it was.
+#include "ngf_host.hpp"
+#include "ngf_uv_train.hpp"
+
+using namespace ngf;
+
+namespace {
+
+constexpr int L = NGF_UV_LAYERS;
+constexpr int kNone = 0, kRelu = 1, kLeaky = 2;
+
+// layer L: inputs, outputs, activation (the order of ngf_uv_desc)
+struct LayerShape { int in, out, act; };
+
+void layer_shapes(int sphere, LayerShape s[L])
+{
+    const int D = sphere ? 3 : 2;
+    int i = 0;
+    s[i++] = {63, 256, kRelu};
+    for (int k = 0; k < 10; ++k) s[i++] = {256, 256, kRelu};
+    s[i++] = {256, 1, kNone};
+    s[i++] = {63, 64, kRelu};
+    s[i++] = {64, 128, kRelu};
+    s[i++] = {128, 128, kRelu};
+    s[i++] = {128, 128, kRelu};
+    s[i++] = {128, D, kNone};
+    s[i++] = {D + 20 * D, 256, kLeaky};
+    for (int k = 0; k < 5; ++k) s[i++] = {256, 256, kLeaky};
+    s[i++] = {256, 3, kNone};
+    s[i++] = {295, 256, kLeaky};
+    for (int k = 0; k < 3; ++k) s[i++] = {256, 256, kLeaky};
+    s[i++] = {256, 3, kNone};
+}
+
+unsigned blocks(int64_t n, int b = 256) { return (unsigned)std::max<int64_t>(1, (n + b - 1) / b); }
+
+}  // namespace
+
+struct ngf_uv_trainer {
+    int device = -1;
+    ngf_uv_train_desc desc{};
+    LayerShape shape[L];
+    int64_t cap = 0;                         // max_rays * max_samples
+    std::vector<void *> allocs;
+    int64_t bytes = 0;
+    // per-sample buffers of the last forward (row counts: cap)
+    float *seg = nullptr, *opac = nullptr, *acct = nullptr, *xraw = nullptr, *uv = nullptr;
+    int32_t *cnt = nullptr, *off = nullptr, *total = nullptr, *list = nullptr, *vid = nullptr;
+    float *in[L] = {};                       // layer inputs (post-activation outputs of the layer before, or encodings)
+    int64_t in_ld[L] = {};
+    float *out[L] = {};                      // layer outputs
+    int64_t out_ld[L] = {};
+    float *Xga = nullptr, *Xg = nullptr, *Xt = nullptr, *X2 = nullptr;
+    // backward
+    float *dP = nullptr, *dR = nullptr, *dH = nullptr, *dXt = nullptr, *dRaw = nullptr, *dC1 = nullptr, *dC2 = nullptr, *dQ = nullptr;
+    float *part = nullptr, *partb = nullptr;
+    float *grads = nullptr;
+    int64_t grad_off[2 * L] = {};
+    int64_t grad_elems = 0;
+    // the last forward
+    const float *raydir = nullptr, *bg = nullptr;
+    float *ray_pos = nullptr;
+    int64_t nrays = 0, R = 0;
+    int32_t S = 0;
+    int64_t ticket = 0, next_ticket = 0;
+    bool have_grads = false;
+};
+
+namespace {
+
+int uvt_alloc(ngf_uv_trainer *t, void **p, size_t bytes)
+{
+    *p = nullptr;
+    if (bytes == 0) bytes = 16;
+    HIP_TRY(hipMalloc(p, bytes));
+    t->allocs.push_back(*p);
+    t->bytes += (int64_t)bytes;
+    return NGF_OK;
+}
+
+template <typename T>
+int uvt_alloc_n(ngf_uv_trainer *t, T **p, int64_t n)
+{
+    void *v = nullptr;
+    int rc = uvt_alloc(t, &v, (size_t)n * sizeof(T));
+    *p = (T *)v;
+    return rc;
+}
+
+void uvt_free(ngf_uv_trainer *t)
+{
+    for (void *p : t->allocs) (void)hipFree(p);
+    t->allocs.clear();
+}
+
+int launch_gemm(const UvtGemm &G, unsigned gx, unsigned gy, unsigned gz, hipStream_t st)
+{
+    hipLaunchKernelGGL(uvt_gemm_kernel, dim3(gx, gy, gz), dim3(256), 0, st, G);
+    HIP_TRY(hipGetLastError());
+    return NGF_OK;
+}
+
+// forward of layer l over `rows` rows (the in-cube count on the device when rows_dev is set)
+int fwd_layer(ngf_uv_trainer *t, int l, int64_t rows, const int32_t *rows_dev, hipStream_t st)
+{
+    const LayerShape &s = t->shape[l];
+    UvtGemm G{};
+    G.A = t->in[l]; G.sam = t->in_ld[l]; G.sak = 1;
+    G.B = t->desc.w[l]; G.sbk = 1; G.sbn = s.in;
+    G.C = t->out[l]; G.ldc = t->out_ld[l];
+    G.bias = t->desc.b[l]; G.act = s.act;
+    G.Mdev = rows_dev;
+    G.M = (int32_t)rows; G.N = s.out; G.K = s.in;
+    return launch_gemm(G, blocks(rows, 64), blocks(s.out, 64), 1, st);
+}
+
+// backward of layer l from dZ (its pre-activation gradient, [rows, out] at ld): dW, db -> the gradient slots; dX (first n_dx input columns) ->
+// dx (ld_dx), + add (ld_add), x act'(in) of the producing layer (act_prev; kNone: no mask)
+int bwd_layer(ngf_uv_trainer *t, int l, const float *dz, int64_t ldz, int64_t rows, const int32_t *rows_dev, float *dx, int64_t ld_dx, int n_dx,
+              const float *add, int64_t ld_add, int act_prev, hipStream_t st)
+{
+    const LayerShape &s = t->shape[l];
+    const int nz = (int)((rows + kUvtChunk - 1) / kUvtChunk);
+    {
+        UvtGemm G{};
+        G.A = dz; G.sam = 1; G.sak = ldz;
+        G.B = t->in[l]; G.sbk = t->in_ld[l]; G.sbn = 1;
+        G.C = t->part; G.ldc = s.in; G.czs = (int64_t)s.out * s.in;
+        G.Mdev = rows_dev;
+        G.M = s.out; G.N = s.in; G.K = (int32_t)rows;
+        G.split = 1; G.chunk = kUvtChunk; G.partb = t->partb;
+        int rc = launch_gemm(G, blocks(s.out, 64), blocks(s.in, 64), (unsigned)std::max(1, nz), st);
+        if (rc) return rc;
+        const int64_t nk = (int64_t)s.out * s.in;
+        hipLaunchKernelGGL(uvt_reduce_kernel, dim3(blocks(nk)), dim3(256), 0, st, (const float *)t->part, (const float *)t->partb, nk, s.out, (int)rows,
+                           rows_dev, t->grads + t->grad_off[2 * l], t->grads + t->grad_off[2 * l + 1]);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!dx) return NGF_OK;
+    UvtGemm G{};
+    G.A = dz; G.sam = ldz; G.sak = 1;
+    G.B = t->desc.w[l]; G.sbk = s.in; G.sbn = 1;
+    G.C = dx; G.ldc = ld_dx;
+    G.add = add; G.ldadd = ld_add;
+    if (act_prev != kNone) { G.aux = t->in[l]; G.ldaux = t->in_ld[l]; G.act = act_prev; }
+    G.Mdev = rows_dev;
+    G.M = (int32_t)rows; G.N = n_dx; G.K = s.out;
+    return launch_gemm(G, blocks(rows, 64), blocks(n_dx, 64), 1, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t ngf_sizeof_uv_train_desc(void) { return (int32_t)sizeof(ngf_uv_train_desc); }
+
+int64_t ngf_uv_trainer_bytes(const ngf_uv_trainer *t) { return t ? t->bytes : 0; }
+
+int ngf_uv_trainer_destroy(ngf_uv_trainer *t)
+{
+    if (!t) return NGF_OK;
+    {
+        DeviceScope ds(t->device);
+        uvt_free(t);
+    }
+    delete t;
+    return NGF_OK;
+}
+
+int ngf_uv_trainer_create(const ngf_uv_train_desc *desc, ngf_uv_trainer **out, void *hip_stream)
+{
+    (void)hip_stream;
+    if (!desc || !out) return fail(NGF_E_ARG, "ngf_uv_trainer_create: null argument");
+    *out = nullptr;
+    const ngf_uv_train_desc &d = *desc;
+    if (d.max_rays <= 0 || d.max_samples <= 0) return fail(NGF_E_ARG, "ngf_uv_trainer_create: max_rays and max_samples must be > 0");
+    if (d.max_rays * (int64_t)d.max_samples >= ((int64_t)1 << 31) / 296)
+        return fail(NGF_E_ARG, "ngf_uv_trainer_create: max_rays * max_samples too large (the buffers are indexed with 32-bit rows)");
+    if (d.flags != 0) return fail(NGF_E_UNSUPPORTED, "ngf_uv_trainer_create: training is fp32 only (flags must be 0)");
+    for (int l = 0; l < L; ++l)
+        if (!d.w[l] || !d.b[l]) return fail(NGF_E_ARG, "ngf_uv_trainer_create: layer %d has no weight or bias", l);
+    int dev = -1;
+    HIP_TRY(hipGetDevice(&dev));
+    ngf_uv_trainer *t = new (std::nothrow) ngf_uv_trainer();
+    if (!t) return fail(NGF_E_ARG, "ngf_uv_trainer_create: out of host memory");
+    t->device = dev;
+    t->desc = d;
+    layer_shapes(d.sphere, t->shape);
+    const int64_t cap = d.max_rays * (int64_t)d.max_samples;
+    t->cap = cap;
+    int rc = NGF_OK;
+    auto F = [&](float **p, int64_t n) { if (!rc) rc = uvt_alloc_n(t, p, n); };
+    auto I = [&](int32_t **p, int64_t n) { if (!rc) rc = uvt_alloc_n(t, p, n); };
+    F(&t->seg, cap); F(&t->opac, cap); F(&t->acct, cap); F(&t->xraw, d.max_rays * 4); F(&t->uv, cap * 3);
+    I(&t->cnt, d.max_rays); I(&t->off, d.max_rays); I(&t->total, 1); I(&t->list, cap); I(&t->vid, cap);
+    F(&t->Xga, cap * 64); F(&t->Xg, cap * 64); F(&t->Xt, cap * 64); F(&t->X2, cap * 296);
+    for (int l = 0; l < L; ++l) {
+        const int o = t->shape[l].out;
+        if (l == 22) { t->out[l] = t->X2; t->out_ld[l] = 296; continue; }        // block1's output is block2.0's input, columns 0..255
+        const int64_t ld = o == 256 ? 256 : (o == 128 ? 128 : (o == 64 ? 64 : (o == 1 ? 1 : 4)));
+        t->out_ld[l] = ld;
+        F(&t->out[l], cap * ld);
+    }
+    if (rc) { uvt_free(t); delete t; return rc; }
+    for (int l = 0; l < L; ++l) {
+        if (l == 0) { t->in[l] = t->Xg; t->in_ld[l] = 64; }
+        else if (l == 12) { t->in[l] = t->Xga; t->in_ld[l] = 64; }
+        else if (l == 17) { t->in[l] = t->Xt; t->in_ld[l] = 64; }
+        else if (l == 23 || l == 24) { t->in[l] = t->X2; t->in_ld[l] = 296; }
+        else { t->in[l] = t->out[l - 1]; t->in_ld[l] = t->out_ld[l - 1]; }
+    }
+    F(&t->dP, cap * 256); F(&t->dR, cap * 256); F(&t->dH, cap * 256); F(&t->dXt, cap * 64);
+    F(&t->dRaw, cap); F(&t->dC1, cap * 4); F(&t->dC2, cap * 4); F(&t->dQ, cap * 4);
+    const int64_t nz = (cap + kUvtChunk - 1) / kUvtChunk;
+    F(&t->part, nz * 256 * 295); F(&t->partb, nz * 256);
+    int64_t g = 0;
+    for (int l = 0; l < L; ++l) {
+        t->grad_off[2 * l] = g; g += (int64_t)t->shape[l].out * t->shape[l].in;
+        t->grad_off[2 * l + 1] = g; g += t->shape[l].out;
+    }
+    t->grad_elems = g;
+    F(&t->grads, g);
+    if (rc) { uvt_free(t); delete t; return rc; }
+    *out = t;
+    return NGF_OK;
+}
+
+int ngf_uv_train_params_changed(ngf_uv_trainer *t)
+{
+    if (!t) return fail(NGF_E_ARG, "ngf_uv_train_params_changed: null handle");
+    return NGF_OK;          // the weights are read in place at every launch: nothing is packed
+}
+
+int ngf_uv_train_forward(ngf_uv_trainer *t, const float *campos, const float *raydir, const float *bg, const float *jitter_u, int32_t n_cams,
+                         int64_t rays_per_cam, int32_t n_samples, float *color, float *trans, float *uv, float *weight, float *ray_pos, int64_t *ticket,
+                         void *hip_stream)
+{
+    if (!t || !campos || !raydir || !jitter_u || !color || !trans || !uv || !weight || !ray_pos || !ticket)
+        return fail(NGF_E_ARG, "ngf_uv_train_forward: null argument");
+    if (n_cams <= 0 || rays_per_cam <= 0 || n_samples <= 0) return fail(NGF_E_ARG, "ngf_uv_train_forward: empty batch");
+    const int64_t nrays = (int64_t)n_cams * rays_per_cam;
+    if (nrays > t->desc.max_rays || n_samples > t->desc.max_samples)
+        return fail(NGF_E_ARG, "ngf_uv_train_forward: %lld rays x %d samples exceed the trainer's %lld x %d", (long long)nrays, n_samples,
+                    (long long)t->desc.max_rays, t->desc.max_samples);
+    DeviceScope ds(t->device);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int S = n_samples;
+    const int64_t M = nrays * S;
+    const int D = t->desc.sphere ? 3 : 2;
+    t->have_grads = false;
+    {
+        UvtRays A{};
+        A.cam = campos; A.raydir = raydir; A.U = jitter_u; A.ray_pos = ray_pos; A.seg = t->seg; A.cnt = t->cnt;
+        A.nrays = nrays; A.R = (int32_t)rays_per_cam; A.S = S;
+        hipLaunchKernelGGL(uvt_rays_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(uvt_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)t->cnt, nrays, t->off, t->total);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(uvt_compact_kernel, dim3(blocks(nrays)), dim3(256), 0, st, (const float *)ray_pos, (const int32_t *)t->off, nrays, S, t->list, t->vid);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(uvt_pe_pos_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)ray_pos, M, t->Xga);
+    HIP_TRY(hipGetLastError());
+    int rc = NGF_OK;
+    // gauge network on every sample -> uv
+    for (int l = 12; l <= 16 && !rc; ++l) rc = fwd_layer(t, l, M, nullptr, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(uvt_uv_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)t->out[16], M, t->desc.sphere, t->uv);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(uv, t->uv, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    // geometry network on the in-cube samples
+    hipLaunchKernelGGL(uvt_gather_kernel, dim3(blocks(M * 64)), dim3(256), 0, st, (const float *)t->Xga, (const int32_t *)t->list, (const int32_t *)t->total,
+                       M, t->Xg);
+    HIP_TRY(hipGetLastError());
+    for (int l = 0; l <= 11 && !rc; ++l) rc = fwd_layer(t, l, M, t->total, st);
+    if (rc) return rc;
+    // texture network on the in-cube samples
+    hipLaunchKernelGGL(uvt_tex_in_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)t->uv, raydir, (const int32_t *)t->list,
+                       (const int32_t *)t->total, M, D, S, t->Xt, t->X2);
+    HIP_TRY(hipGetLastError());
+    for (int l = 17; l <= 28 && !rc; ++l) rc = fwd_layer(t, l, M, t->total, st);
+    if (rc) return rc;
+    {
+        UvtComp A{};
+        A.seg = t->seg; A.vid = t->vid; A.raw = t->out[11]; A.c1 = t->out[23]; A.c2 = t->out[28]; A.bg = bg;
+        A.color = color; A.trans = trans; A.weight = weight; A.opac = t->opac; A.acct = t->acct; A.xraw = t->xraw;
+        A.nrays = nrays; A.R = (int32_t)rays_per_cam; A.S = S;
+        hipLaunchKernelGGL(uvt_composite_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    t->raydir = raydir; t->bg = bg; t->ray_pos = ray_pos;
+    t->nrays = nrays; t->R = rays_per_cam; t->S = S;
+    t->ticket = ++t->next_ticket;
+    *ticket = t->ticket;
+    return NGF_OK;
+}
+
+int ngf_uv_train_backward(ngf_uv_trainer *t, int64_t ticket, const float *d_color, const float *d_trans, const float *d_uv, const float *d_weight,
+                          void *hip_stream)
+{
+    if (!t || !d_color || !d_trans) return fail(NGF_E_ARG, "ngf_uv_train_backward: null argument");
+    if (ticket <= 0 || ticket != t->ticket) return fail(NGF_E_STALE, "ngf_uv_train_backward: ticket %lld is not the trainer's last forward (%lld)",
+                                                        (long long)ticket, (long long)t->ticket);
+    DeviceScope ds(t->device);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int64_t nrays = t->nrays, M = nrays * t->S;
+    {
+        UvtComp A{};
+        A.seg = t->seg; A.vid = t->vid; A.raw = t->out[11]; A.c1 = t->out[23]; A.c2 = t->out[28]; A.bg = t->bg;
+        A.opac = t->opac; A.acct = t->acct; A.xraw = t->xraw;
+        A.d_color = d_color; A.d_trans = d_trans; A.d_weight = d_weight;
+        A.d_raw = t->dRaw; A.d_c1 = t->dC1; A.d_c2 = t->dC2;
+        A.nrays = nrays; A.R = (int32_t)t->R; A.S = t->S;
+        hipLaunchKernelGGL(uvt_composite_bwd_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    const int32_t *V = t->total;
+    int rc = NGF_OK;
+    float *pp[2] = {t->dP, t->dR};
+    // block2: 28 (dC2) -> 27 -> 26 -> 25 -> 24, whose input gradient (columns 0..255, the block1 output) goes to dH
+    rc = bwd_layer(t, 28, t->dC2, 4, M, V, pp[0], 256, 256, nullptr, 0, kLeaky, st);
+    int cur = 0;
+    for (int l = 27; l >= 25 && !rc; --l, cur ^= 1) rc = bwd_layer(t, l, pp[cur], 256, M, V, pp[cur ^ 1], 256, 256, nullptr, 0, kLeaky, st);
+    if (!rc) rc = bwd_layer(t, 24, pp[cur], 256, M, V, t->dH, 256, 256, nullptr, 0, kNone, st);
+    // color1: its input gradient + block2.0's, x LeakyReLU'(block1 output)
+    if (!rc) rc = bwd_layer(t, 23, t->dC1, 4, M, V, pp[0], 256, 256, t->dH, 256, kLeaky, st);
+    cur = 0;
+    for (int l = 22; l >= 18 && !rc; --l, cur ^= 1) rc = bwd_layer(t, l, pp[cur], 256, M, V, pp[cur ^ 1], 256, 256, nullptr, 0, kLeaky, st);
+    if (!rc) rc = bwd_layer(t, 17, pp[cur], 256, M, V, t->dXt, 64, t->shape[17].in, nullptr, 0, kNone, st);
+    if (rc) return rc;
+    // d uv -> d q (every sample), gauge network
+    hipLaunchKernelGGL(uvt_uv_bwd_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)t->out[16], (const float *)t->uv, (const float *)t->dXt,
+                       (const int32_t *)t->vid, d_uv, M, t->desc.sphere, t->dQ);
+    HIP_TRY(hipGetLastError());
+    rc = bwd_layer(t, 16, t->dQ, 4, M, nullptr, pp[0], 128, 128, nullptr, 0, kRelu, st);
+    cur = 0;
+    for (int l = 15; l >= 13 && !rc; --l, cur ^= 1)
+        rc = bwd_layer(t, l, pp[cur], t->out_ld[l], M, nullptr, pp[cur ^ 1], t->in_ld[l], t->shape[l].in, nullptr, 0, kRelu, st);
+    if (!rc) rc = bwd_layer(t, 12, pp[cur], 64, M, nullptr, nullptr, 0, 0, nullptr, 0, kNone, st);
+    // geometry: 11 (d raw density) -> ... -> 0
+    if (!rc) rc = bwd_layer(t, 11, t->dRaw, 1, M, V, pp[0], 256, 256, nullptr, 0, kRelu, st);
+    cur = 0;
+    for (int l = 10; l >= 1 && !rc; --l, cur ^= 1) rc = bwd_layer(t, l, pp[cur], 256, M, V, pp[cur ^ 1], 256, 256, nullptr, 0, kRelu, st);
+    if (!rc) rc = bwd_layer(t, 0, pp[cur], 256, M, V, nullptr, 0, 0, nullptr, 0, kNone, st);
+    if (rc) return rc;
+    t->have_grads = true;
+    return NGF_OK;
+}
+
+int ngf_uv_train_get_grads(ngf_uv_trainer *t, float *const out[NGF_UV_TRAIN_PARAMS], void *hip_stream)
+{
+    if (!t || !out) return fail(NGF_E_ARG, "ngf_uv_train_get_grads: null argument");
+    if (!t->have_grads) return fail(NGF_E_ARG, "ngf_uv_train_get_grads: no backward since the last forward");
+    DeviceScope ds(t->device);
+    hipStream_t st = (hipStream_t)hip_stream;
+    for (int k = 0; k < NGF_UV_TRAIN_PARAMS; ++k) {
+        if (!out[k]) continue;
+        const int l = k / 2;
+        const int64_t n = (k & 1) ? t->shape[l].out : (int64_t)t->shape[l].out * t->shape[l].in;
+        HIP_TRY(hipMemcpyAsync(out[k], t->grads + t->grad_off[k], (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    return NGF_OK;
+}
+
+}  // extern "C"

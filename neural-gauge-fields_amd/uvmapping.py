@@ -1,13 +1,17 @@
 """``NeuTex`` -- drop-in for the colour path of the reference's UV-Mapping model (UV-Mapping/model/model.py:11-59).
 
 Same sub-module and parameter names as the reference (``net_geometry_decoder.block.*``,
-``gauge_transform.encoder.*``, ``net_texture.{block1,color1,block2}.*``) so its ``{epoch}_net_NeuTex.pth``
-checkpoints load (``strict=False`` skips ``inverse_gauge.*``, which only feeds training losses, model.py:335-350).
+``gauge_transform.encoder.*``, ``net_texture.{block1,color1,block2}.*``, ``inverse_gauge.inverse_network.*``) so its
+``{epoch}_net_NeuTex.pth`` checkpoints load with ``strict=True`` (``load_params`` keeps ``strict=False`` for parameter sets without
+the inverse network).
 ``forward`` returns the reference's ``color`` / ``transmittance`` outputs; the three MLPs, the cube ray generation
 and the ray march run in one HIP kernel (include/ngf.h: ngf_uv_render).
 
 The reference jitters the segment lengths with ``torch.rand`` even at test time (model.py:30); pass ``jitter_u``
 ([N,R,S] uniforms) for reproducible output, otherwise they are drawn on the device.
+
+Training: with ``net.differentiable = True`` (an attribute, never saved) and grad enabled, ``forward`` returns the reference's training dict
+with a graph over every parameter (uv_train.py, include/ngf.h: ngf_uv_trainer_*).  Off, or under ``torch.no_grad()``, it is the eval path.
 """
 from __future__ import annotations
 
@@ -15,6 +19,7 @@ import ctypes as C
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 
@@ -72,8 +77,59 @@ class TextureMlpDecoder(nn.Module):
         self.block2 = _seq([width + 3 + 36] + [width] * 4 + [3], (lambda: nn.LeakyReLU(0.2), False))
 
 
+class InverseNetwork(nn.Module):
+    """gauge_fields.py:78-119 (modified AtlasNet core): template point (2|3) -> 64 -> 512 -> 512 -> 512 -> xyz, ReLU.  Plain torch: at the
+    shipped configuration it sees only the template points of the origin loss."""
+
+    def __init__(self, input_point_dim, mid_size=64, hidden_size=512, num_layers=2):
+        super().__init__()
+        self.input_size = input_point_dim
+        self.linear1 = nn.Linear(input_point_dim, mid_size)
+        self.linear2 = nn.Linear(mid_size, hidden_size)
+        self.linear_list = nn.ModuleList([nn.Linear(hidden_size, hidden_size) for _ in range(num_layers)])
+        self.last_linear = nn.Linear(hidden_size, 3)
+
+    def forward(self, x):
+        x = F.relu(self.linear1(x))
+        x = F.relu(self.linear2(x))
+        for lin in self.linear_list:
+            x = F.relu(lin(x))
+        return self.last_linear(x)
+
+
+class InverseGauge(nn.Module):
+    """gauge_fields.py:164-207.  ``forward(template_points=None)`` -> (input points [P,D], output points [1,1,P,3]); the points are drawn as
+    SquareTemplate / SphereTemplate.get_random_points do, on the parameters' device.  ``map(uv)`` [..., D] -> [..., 3]: the reference's
+    ``uv.view(input_shape, -1, D)`` raises in torch, so the evident intent -- the network on the flattened points -- is what runs here."""
+
+    def __init__(self, num_points_per_primitive, primitive_type="square"):
+        super().__init__()
+        if primitive_type not in ("square", "sphere"):
+            raise ValueError(f"Unknown primitive type {primitive_type}")
+        self.primitive_type = primitive_type
+        self.input_point_dim = 2 if primitive_type == "square" else 3
+        self.num_points_per_primitive = int(num_points_per_primitive)
+        self.inverse_network = InverseNetwork(self.input_point_dim)
+
+    def random_points(self, n):
+        dev = self.inverse_network.linear1.weight.device
+        with torch.no_grad():
+            if self.primitive_type == "square":
+                return torch.rand((n, 2), device=dev) * 2 - 1
+            return F.normalize(torch.randn((n, 3), device=dev) * 2 - 1, dim=-1)
+
+    def forward(self, template_points=None):
+        pts = self.random_points(self.num_points_per_primitive) if template_points is None else template_points
+        return pts, self.inverse_network(pts.unsqueeze(0)).unsqueeze(1).contiguous()
+
+    def map(self, uv):
+        assert uv.shape[-1] == self.input_point_dim
+        out = self.inverse_network(uv.reshape(-1, self.input_point_dim))
+        return out.view(uv.shape[:-1] + (3,))
+
+
 class NeuTex(nn.Module):
-    def __init__(self, opt=None, primitive_type=None, sample_num=None, device='cuda', split_bf16=False):
+    def __init__(self, opt=None, primitive_type=None, sample_num=None, device='cuda', split_bf16=False, points_per_primitive=None):
         super().__init__()
         self.opt = opt
         self.split_bf16 = bool(split_bf16)          # NGF_UV_F_SPLIT_BF16: 256-unit layers as 3-term split bf16 MFMA products (opt-in)
@@ -83,6 +139,10 @@ class NeuTex(nn.Module):
         self.net_geometry_decoder = GeometryMlpDecoder(pos_freqs=10, hidden_size=256, num_layers=10)
         self.gauge_transform = GaugeTransform(self.primitive_type)
         self.net_texture = TextureMlpDecoder(2 if self.primitive_type == 'square' else 3)
+        ppp = points_per_primitive if points_per_primitive is not None else getattr(opt, 'points_per_primitive', None)
+        self.inverse_gauge = InverseGauge(2500 if ppp is None else int(ppp), self.primitive_type)
+        self.differentiable = False          # training switch (uv_train.py): an attribute, not a parameter or buffer; never saved
+        self._uv_engine = None
         self._handle = None
         self._key = None
         self.to(device)
@@ -148,11 +208,12 @@ class NeuTex(nn.Module):
     def __del__(self):
         try:
             self.release()
+            self.release_grad_engine()
         except Exception:
             pass
 
     def handle(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        key = tuple((t.data_ptr(), t._version) for lin in self.layers() for t in (lin.weight, lin.bias))     # the 29 render layers only
         if self._handle is not None and key == self._key:
             return self._handle
         dev = torch.device(self.device)
@@ -175,10 +236,63 @@ class NeuTex(nn.Module):
         self._push_texture()
         return out
 
+    # --- training (uv_train.py) ---------------------------------------------------------------------------------------------------
+    def _uv_grad_engine(self, nrays, S):
+        from .uv_train import UvGrad, train_params
+        e = self._uv_engine
+        if e is None or e._h is None or not e.fits(nrays, S, train_params(self)):
+            # a live engine that is too small grows to the larger of both shapes, so alternating batch shapes settle on one engine
+            old = (e.max_rays, e.max_samples) if e is not None and e._h is not None else (0, 0)
+            if e is not None:
+                e.release()
+            self._uv_engine = None
+            self._uv_engine = UvGrad(self, max(nrays, old[0]), max(S, old[1]))
+        return self._uv_engine
+
+    def release_grad_engine(self):
+        """Free the training engine's per-sample buffers (the next differentiable forward builds a new one)."""
+        if self._uv_engine is not None:
+            self._uv_engine.release()
+            self._uv_engine = None
+
+    def _train_forward(self, camera_position, ray_direction, background_color, jitter_u, template_points):
+        from .uv_train import TrainOutput, _UvRender, train_params
+        if self.split_bf16:
+            raise RuntimeError("UV-Mapping training is fp32: construct the NeuTex with split_bf16=False to train it")
+        if getattr(self.net_texture, "cubemap_", None) is not None:
+            raise RuntimeError("UV-Mapping training does not support texture editing: clear it with set_target_texture(None)")
+        params = train_params(self)
+        dev = params[0].device
+        if dev.type != 'cuda':
+            raise RuntimeError("a differentiable NeuTex renders on the GPU only (device='cuda'); there is no CPU path")
+        rd = ray_direction.detach().to(dev, torch.float32).contiguous()
+        N, R = rd.shape[0], rd.shape[1]
+        S = self.sample_num
+        U = (torch.rand((N, R, S), device=dev) if jitter_u is None else jitter_u).detach().to(dev, torch.float32).contiguous()
+        if tuple(U.shape) != (N, R, S):
+            raise ValueError(f"jitter_u must be [N,R,S] = [{N},{R},{S}]")
+        cam = camera_position.detach().to(dev, torch.float32).contiguous()
+        bg = None if background_color is None else background_color.detach().to(dev, torch.float32).contiguous()
+        if tuple(cam.shape) != (N, 3) or (bg is not None and tuple(bg.shape) != (N, 3)):
+            raise ValueError(f"camera_position / background_color must be [N,3] with N = {N}")
+        eng = self._uv_grad_engine(N * R, S)
+        color, trans, uv, weight, pos = _UvRender.apply(self, eng, cam, rd, bg, U, *params)
+        _, points_3d = self.inverse_gauge(None if template_points is None else template_points.to(dev, torch.float32))
+        points = points_3d.view(points_3d.shape[0], -1, points_3d.shape[-1]).permute(0, 2, 1)
+        return TrainOutput(self, uv, points=points, color=color, transmittance=trans, points_original=pos, points_inverse_weights=weight, uv=uv)
+
+    def forward(self, camera_position=None, ray_direction=None, background_color=None, jitter_u=None, debug=False, collect_stats=False,
+                template_points=None):
+        """model.py:27: camera_position [N,3], ray_direction [N,R,3] (normalised), background_color [N,3] or None.  With ``differentiable`` set
+        and grad enabled: the training dict (color, transmittance, points, points_original, points_inverse_weights, uv, lazy points_inverse)."""
+        if self.differentiable and torch.is_grad_enabled():
+            if debug or collect_stats:
+                raise ValueError("debug / collect_stats belong to the eval path (torch.no_grad() or differentiable = False)")
+            return self._train_forward(camera_position, ray_direction, background_color, jitter_u, template_points)
+        return self._eval_forward(camera_position, ray_direction, background_color, jitter_u, debug, collect_stats)
+
     @torch.no_grad()
-    def forward(self, camera_position=None, ray_direction=None, background_color=None, jitter_u=None, debug=False,
-                collect_stats=False):
-        """model.py:27: camera_position [N,3], ray_direction [N,R,3] (normalised), background_color [N,3] or None."""
+    def _eval_forward(self, camera_position, ray_direction, background_color, jitter_u, debug, collect_stats):
         dev = torch.device(self.device)
         N, R = ray_direction.shape[0], ray_direction.shape[1]
         S = self.sample_num
