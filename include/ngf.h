@@ -389,6 +389,19 @@ int ngf_uv_destroy(ngf_uv *m);
 int ngf_uv_set_texture(ngf_uv *m, const float *tex, int32_t faces, int32_t H, int32_t W, int32_t C, int32_t mode,
                        void *hip_stream);
 int ngf_uv_texture_edit(const ngf_uv *m, const float *uv, const float *orig, int64_t n, float *out, void *hip_stream);
+/* Texture export: TextureMlpDecoder.forward (decoder.py:56-121) on n explicit points, the hot path of net_texture.export_textures /
+ * _export_cube / _export_sphere / _export_square (decoder.py:123-179).  uv [n,3] (z ignored for square models), out [n,3], all device floats.
+ *   flags = 0 (view mode): (softplus(color1) + color2).clamp(min=0); view = ONE direction float[3] (view_stride 0) or one per point [n,3]
+ *     (view_stride 3), device memory, used as given (not normalised).  With an edit texture set (ngf_uv_set_texture) the colour goes through
+ *     the edit stage, as in the reference's forward.
+ *   flags = NGF_UV_TEX_DIFFUSE: the exporters' viewdir=None branch, sigmoid(color1(block1(uv))); view is ignored (may be NULL), block2 does
+ *     not run and no edit stage applies.
+ * Reads the weights of the handle (no copy), fp32 on the matrix pipe; a handle created with NGF_UV_F_SPLIT_BF16 is served by the SAME fp32
+ * path (its fp32 weight images are always present).  No atomics: a call's output depends on its inputs alone, bit for bit.  The handle's
+ * state is not touched.  Returns NGF_E_ARG on null / invalid arguments without touching a GPU. */
+enum { NGF_UV_TEX_DIFFUSE = 1 };
+int ngf_uv_texture_eval(const ngf_uv *m, const float *uv, const float *view, int32_t view_stride, int64_t n, int32_t flags, float *out,
+                        void *hip_stream);
 /* Replaces NeuTex.forward's colour outputs for one camera (model.py:30-52):
  *   campos_host float[3], bg_host float[3] or NULL (HOST pointers), raydir [R,3], jitter_u [R,S] = the uniforms
  *   cube_ray_generation draws with torch.rand (renderer.py:112-117; jitter = 0.05 always, model.py:30);

@@ -28,7 +28,7 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_infoinv_trainer_create", "ngf_infoinv_trainer_destroy", "ngf_infoinv_trainer_bytes", "ngf_sizeof_infoinv_train_desc",
            "ngf_infoinv_train_forward", "ngf_infoinv_train_backward_grad", "ngf_infoinv_train_get_grads", "ngf_infoinv_train_params_changed",
            "ngf_uv_trainer_create", "ngf_uv_trainer_destroy", "ngf_uv_trainer_bytes", "ngf_sizeof_uv_train_desc", "ngf_uv_train_forward",
-           "ngf_uv_train_backward", "ngf_uv_train_get_grads", "ngf_uv_train_params_changed"]
+           "ngf_uv_train_backward", "ngf_uv_train_get_grads", "ngf_uv_train_params_changed", "ngf_uv_texture_eval"]
 
 
 class FieldDesc(C.Structure):
@@ -55,6 +55,7 @@ class UvDesc(C.Structure):
 
 
 UV_F_SPLIT_BF16 = 1
+UV_TEX_DIFFUSE = 1          # ngf_uv_texture_eval flags
 
 
 def build(force: bool = False) -> str:
@@ -107,6 +108,7 @@ def _load(path):
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngf_uv_set_texture.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.ngf_uv_texture_edit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.ngf_uv_texture_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.ngf_pack_mask_bits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ngf_resize_bilinear.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         L.ngf_eval_workspace_bytes.restype = C.c_int64

@@ -252,6 +252,15 @@ extern "C" int ngf_uv_texture_edit(const ngf_uv *m, const float *uv, const float
     return NGF_OK;
 }
 
+// what ngf_uv_export.hip needs of a handle (declared in ngf_uv_export.hpp)
+namespace ngf {
+const UvArgs &uv_handle_args(const ::ngf_uv *m, int *num_cus)
+{
+    *num_cus = m->num_cus;
+    return m->proto;
+}
+}  // namespace ngf
+
 static int uv_launch(const ngf_uv *m, UvArgs &A, hipStream_t st)
 {
     const unsigned slot = m->next_counter.fetch_add(1) % kCounters;

@@ -192,7 +192,9 @@ __device__ __forceinline__ void uv_texture_edit(const float *tex, int H, int W, 
     }
 }
 
-// elementwise form of the edit stage (ngf_uv_texture_edit: utility + parity hook)
+// elementwise form of the edit stage (ngf_uv_texture_edit: utility + parity hook); a plain (non-template) kernel: ngf_uv.hip alone defines it,
+// another translation unit that includes this header (ngf_uv_export.hpp) sets NGF_UV_NO_EDIT_KERNEL
+#ifndef NGF_UV_NO_EDIT_KERNEL
 __global__ void __launch_bounds__(256) uv_texture_edit_kernel(const float *tex, int H, int W, int C, int mode, int sphere, const float *uv, const float *orig,
                                                               int64_t n, float *out)
 {
@@ -204,6 +206,7 @@ __global__ void __launch_bounds__(256) uv_texture_edit_kernel(const float *tex, 
         out[i * 3] = c[0]; out[i * 3 + 1] = c[1]; out[i * 3 + 2] = c[2];
     }
 }
+#endif
 
 constexpr int kUvQLayer = 8 * 4 * 12 * 64 * 4;      // floats of one 256 -> 256 layer's split-bf16 image: [8 k-blocks][4 groups][12 fragments][64 lanes][8 bf16]
 constexpr int kUvActSteps = 80;                    // k-steps of per-wave activation storage (74 used by block2.0)

@@ -10,13 +10,19 @@ and the ray march run in one HIP kernel (include/ngf.h: ngf_uv_render).
 The reference jitters the segment lengths with ``torch.rand`` even at test time (model.py:30); pass ``jitter_u``
 ([N,R,S] uniforms) for reproducible output, otherwise they are drawn on the device.
 
+Texture export: ``net.net_texture.export_textures`` / ``_export_cube`` / ``_export_sphere`` / ``_export_square`` (decoder.py:123-179) and the
+general ``NeuTex.texture_colors`` run the texture MLP on explicit points in a HIP kernel of their own (include/ngf.h: ngf_uv_texture_eval);
+``merge_cube_to_single_texture`` (util.py:286-312) lays a cube export out as the cross image the reference's test driver saves.
+
 Training: with ``net.differentiable = True`` (an attribute, never saved) and grad enabled, ``forward`` returns the reference's training dict
 with a graph over every parameter (uv_train.py, include/ngf.h: ngf_uv_trainer_*).  Off, or under ``torch.no_grad()``, it is the eval path.
 """
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -64,17 +70,104 @@ class GaugeTransform(nn.Module):
         self.encoder = GaugeNetwork(3, self.output_dim)
 
 
+# --- the sample points of the texture exporters (decoder.py:123-170), built as the reference builds them so that they are its points bit for bit:
+# float64 numpy grids rounded to float32 once, the cube faces normalised in float32 on the CPU.  A few MB per export, not the hot path.
+def _cell_centres(resolution):
+    """generate_grid(2, R) (util.py:13-16): [R,R,2] cell centres in (-1,1), 'ij' order, float64."""
+    a = np.arange(resolution)
+    grid = np.stack(np.meshgrid(a, a, indexing="ij"), axis=-1)
+    return (2 * grid + 1) / resolution - 1
+
+
+def export_square_points(resolution):
+    """[R,R,2] float32: the points of ``_export_square``; texel [i,j] is evaluated at uv = (centre i, centre j)."""
+    return torch.tensor(_cell_centres(resolution)).float()
+
+
+def export_cube_points(resolution):
+    """[6,R,R,3] float32: the points of ``_export_cube`` -- convert_cube_uv_to_xyz (util.py:134-164) of the cell centres per face."""
+    vc, uc = export_square_points(resolution).unbind(-1)
+    one = torch.ones_like(uc)
+    faces = ((one, vc, -uc), (-one, vc, uc), (uc, one, -vc), (uc, -one, vc), (uc, vc, one), (-uc, vc, -one))
+    return torch.stack([F.normalize(torch.stack(f, dim=-1), dim=-1) for f in faces], dim=0)
+
+
+def export_sphere_points(resolution):
+    """[R,2R,3] float32: the equirectangular directions of ``_export_sphere``, before its final ``flip(0)``."""
+    grid = np.stack(np.meshgrid(np.arange(2 * resolution), np.arange(resolution), indexing="xy"), axis=-1)
+    grid = grid / np.array([2 * resolution, resolution]) * np.array([2 * np.pi, np.pi]) + np.array([np.pi, 0])
+    x, y = grid[..., 0], grid[..., 1]
+    return torch.tensor(np.stack([-np.sin(x) * np.sin(y), -np.cos(y), -np.cos(x) * np.sin(y)], -1)).float()
+
+
+def merge_cube_to_single_texture(cube, flip=True, rotate=True):
+    """util.py:286-312: a [6,R,R,C] cube export laid out as a [3R,4R,C] cross (unused cells 1); pure indexing on ``cube``'s device."""
+    assert cube.shape[0] == 6 and cube.shape[1] == cube.shape[2]
+    res = cube.shape[1]
+    result = torch.ones((3 * res, 4 * res, cube.shape[-1]), dtype=cube.dtype, device=cube.device)
+    if flip:
+        cube = cube.flip(1)
+    row = [0, 5, 1, 4] if rotate else [1, 4, 0, 5]
+    for k, face in enumerate(row):
+        result[res:2 * res, k * res:(k + 1) * res] = cube[face]
+    result[:res, res:2 * res] = cube[2].flip(0, 1) if rotate else cube[2]
+    result[2 * res:, res:2 * res] = cube[3].flip(0, 1) if rotate else cube[3]
+    return result
+
+
 class TextureMlpDecoder(nn.Module):
     """decoder.py:11-58: the MLPs; ``cubemap_`` / ``cubemap_mode_`` (texture editing) are plain attributes as in the
-    reference and are pushed to the device by NeuTex.set_target_texture."""
+    reference and are pushed to the device by NeuTex.set_target_texture.  The exporters (decoder.py:123-179) are thin callers of the owning
+    NeuTex's ``texture_colors``: the MLP runs in the HIP kernel behind it, on the owner's handle (``_owner``: a weak reference set by
+    NeuTex.__init__, a plain attribute -- no parameter, buffer or state-dict key)."""
 
     def __init__(self, uv_dim, width=256):
         super().__init__()
         self.cubemap_ = None
         self.cubemap_mode_ = 0
+        self.uv_dim = uv_dim
+        self._owner = None
+        self._points = {}                # kind -> (resolution, device, points): the last export's sample points stay on the device
         self.block1 = _seq([uv_dim + 20 * uv_dim] + [width] * 6, (lambda: nn.LeakyReLU(0.2), True))
         self.color1 = nn.Linear(width, 3)
         self.block2 = _seq([width + 3 + 36] + [width] * 4 + [3], (lambda: nn.LeakyReLU(0.2), False))
+
+    def __getstate__(self):              # (a weak reference does not pickle; NeuTex.__setstate__ restores it)
+        d = self.__dict__.copy()
+        d["_owner"], d["_points"] = None, {}
+        return d
+
+    def _net(self):
+        net = self._owner() if self._owner is not None else None
+        if net is None:
+            raise RuntimeError("this TextureMlpDecoder belongs to no live NeuTex: the exporters run on the owning model's GPU handle (keep the model alive)")
+        if torch.device(net.device).type != 'cuda':
+            raise RuntimeError("ngf_amd NeuTex exports textures on the GPU only (device='cuda'); there is no CPU path")
+        return net
+
+    def _export(self, kind, build, resolution, viewdir):
+        net = self._net()
+        dev = torch.device(net.device)
+        hit = self._points.get(kind)
+        if hit is None or hit[0] != int(resolution) or hit[1] != dev:
+            hit = (int(resolution), dev, build(int(resolution)).to(dev))
+            self._points[kind] = hit
+        return net.texture_colors(hit[2], viewdir, diffuse=viewdir is None)
+
+    def _export_cube(self, resolution, viewdir):
+        """[6,R,R,3]; ``viewdir`` a 3-vector (used as given, not normalised) or None for the diffuse texture sigmoid(color1)."""
+        return self._export("cube", export_cube_points, resolution, viewdir)
+
+    def _export_sphere(self, resolution, viewdir):
+        """[R,2R,3] equirectangular."""
+        return self._export("sphere", export_sphere_points, resolution, viewdir).flip(0)
+
+    def _export_square(self, resolution, viewdir):
+        """[R,R,3], indexed [i <-> uv[...,0], j <-> uv[...,1]] as the reference's (the transpose of what sample_square reads back)."""
+        return self._export("square", export_square_points, resolution, viewdir)
+
+    def export_textures(self, resolution=512, viewdir=[0, 0, 1]):
+        return self._export_cube(resolution, viewdir) if self.uv_dim == 3 else self._export_square(resolution, viewdir)
 
 
 class InverseNetwork(nn.Module):
@@ -139,6 +232,7 @@ class NeuTex(nn.Module):
         self.net_geometry_decoder = GeometryMlpDecoder(pos_freqs=10, hidden_size=256, num_layers=10)
         self.gauge_transform = GaugeTransform(self.primitive_type)
         self.net_texture = TextureMlpDecoder(2 if self.primitive_type == 'square' else 3)
+        self.net_texture._owner = weakref.ref(self)
         ppp = points_per_primitive if points_per_primitive is not None else getattr(opt, 'points_per_primitive', None)
         self.inverse_gauge = InverseGauge(2500 if ppp is None else int(ppp), self.primitive_type)
         self.differentiable = False          # training switch (uv_train.py): an attribute, not a parameter or buffer; never saved
@@ -199,6 +293,49 @@ class NeuTex(nn.Module):
             _lib.check(_lib.lib().ngf_uv_texture_edit(self.handle(), uv.data_ptr(), oc.data_ptr(), uv.shape[0], out.data_ptr(),
                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out
+
+    @torch.no_grad()
+    def texture_colors(self, uv, view_dir=None, diffuse=False):
+        """TextureMlpDecoder.forward (decoder.py:56-121) on explicit points: uv [..., D] (D = 3; a square model also takes D = 2 and ignores z)
+        and ``view_dir``, one 3-vector shared by all points or [..., 3] per point, used as given -> [..., 3] on the model's device:
+        ``(softplus(color1) + color2).clamp(min=0)``, through the edit stage when a target texture is set.  ``diffuse=True`` is the exporters'
+        viewdir=None branch, ``sigmoid(color1(block1(uv)))``: no view direction, no edit stage."""
+        dev = torch.device(self.device)
+        if dev.type != 'cuda':
+            raise RuntimeError("ngf_amd NeuTex exports textures on the GPU only (device='cuda'); there is no CPU path")
+        uv = torch.as_tensor(uv)
+        D = uv.shape[-1]
+        if D != 3 and not (D == 2 and self.primitive_type == 'square'):
+            raise ValueError(f"uv must be [..., 3]{' or [..., 2]' if self.primitive_type == 'square' else ''}, got {tuple(uv.shape)}")
+        lead = tuple(uv.shape[:-1])
+        pts = uv.detach().to(dev, torch.float32).reshape(-1, D)
+        if D == 2:
+            pts = torch.cat([pts, pts.new_zeros((pts.shape[0], 1))], dim=-1)
+        pts = pts.contiguous()
+        n = pts.shape[0]
+        view, stride = None, 0
+        if not diffuse:
+            if view_dir is None:
+                raise ValueError("texture_colors needs a view direction unless diffuse=True")
+            view = torch.as_tensor(view_dir).detach().to(dev, torch.float32)
+            if view.shape[-1] != 3:
+                raise ValueError(f"view_dir must be a 3-vector or [..., 3], got {tuple(view.shape)}")
+            if view.numel() == 3:
+                view = view.reshape(3).contiguous()
+            else:
+                view, stride = view.expand(lead + (3,)).reshape(-1, 3).contiguous(), 3
+        out = torch.empty((n, 3), device=dev)
+        if n:
+            h = self.handle()
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().ngf_uv_texture_eval(h, pts.data_ptr(), None if view is None else view.data_ptr(), stride, n,
+                                                          _lib.UV_TEX_DIFFUSE if diffuse else 0, out.data_ptr(),
+                                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out.view(lead + (3,))
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.net_texture._owner = weakref.ref(self)
 
     def release(self):
         if self._handle is not None:
