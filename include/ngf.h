@@ -360,6 +360,32 @@ int ngf_infoinv_train_backward_grad(ngf_infoinv_trainer *t, int64_t ticket, cons
 int ngf_infoinv_train_get_grads(ngf_infoinv_trainer *t, float *const out[NGF_INFOINV_TRAIN_PARAMS], void *hip_stream);
 /* after writing to a plane's memory (optimizer.step(), checkpoint load, in-place edit): the next forward re-packs the planes */
 int ngf_infoinv_train_params_changed(ngf_infoinv_trainer *t);
+/* The fused step on the same handle: the loop body of InfoInv/main.py:262-330 with the rgb loss and torch.optim.Adam inside the library.  One
+ * trainer serves this and the autograd path above; no call below synchronises anything or allocates -- they enqueue on hip_stream and return.
+ * Any ngf_infoinv_train_forward after a step_backward retires its gradients (get_grad / adam_all then return NGF_E_ARG).
+ * step_backward: the forward above, then rgb_loss = mean((rgb_map - rgb_train)^2): loss_out[0] = the sum of squared residuals, loss_out[1] =
+ *   the mean (two doubles, DEVICE), d rgb_map = 2 (rgb_map - rgb_train) / (3 n) handed straight to the backward, the per-sample deltas and the
+ *   fixed-point plane scatter of the autograd path, and the weight gradients on the matrix pipe (v_mfma_f32_16x16x4_f32: fp32 sums over 1024
+ *   rows, added in row order in fp64; every bias in fp64).  No float atomics: two calls from one state leave bit-identical gradients.  n may
+ *   exceed the trainer's max_rays: the batch is then worked through in ray chunks whose gradients add up before the one Adam call.
+ * set_moments: the caller's Adam moments (exp_avg / exp_avg_sq, DEVICE, float32, the parameters' layouts; all sixteen) that adam_all updates.
+ * adam_all: torch.optim.Adam's arithmetic (betas, eps; no weight decay, no amsgrad) on the gradients of the last step_backward.  A plane is one
+ *   pass: fixed-point accumulator and device-side scale in, + l1_weight * sign(p) / numel(plane) (sign(0) = 0), parameter, both moments and the
+ *   trainer's packed channel-last copy out, so the next forward packs nothing.  step_count[k] = the parameter's step number t (bias
+ *   corrections 1 - beta^t), 0 = leave it alone (frozen / no gradient).  A non-finite gradient scale gives NaN gradients, never wrapped integers.
+ * get_grad: one parameter's gradient of the last step_backward in the reference layout (planes without the L1 term); tests and inspection.
+ * adam_ext: the same update from the CALLER'S gradients and moments (torch's p.grad, state['exp_avg'], state['exp_avg_sq']; grad[k] NULL or
+ *   step_count[k] = 0 = skip), no L1 term added: the caller's loss put it into the gradient.  ngf_amd.optim.Adam is its Python face. */
+int ngf_infoinv_train_step_backward(ngf_infoinv_trainer *t, const float *rays, const float *rgb_train, const float *jitter, int64_t n, int32_t n_samples,
+                                    int32_t white_bg, int32_t infoinv, double *loss_out, void *hip_stream);
+int ngf_infoinv_train_set_moments(ngf_infoinv_trainer *t, float *const exp_avg[NGF_INFOINV_TRAIN_PARAMS],
+                                  float *const exp_avg_sq[NGF_INFOINV_TRAIN_PARAMS]);
+int ngf_infoinv_train_adam_all(ngf_infoinv_trainer *t, const int32_t step_count[NGF_INFOINV_TRAIN_PARAMS], const float lr[NGF_INFOINV_TRAIN_PARAMS],
+                               float beta1, float beta2, float eps, float l1_weight, void *hip_stream);
+int ngf_infoinv_train_get_grad(ngf_infoinv_trainer *t, int32_t which, float *out, void *hip_stream);
+int ngf_infoinv_train_adam_ext(ngf_infoinv_trainer *t, const float *const grad[NGF_INFOINV_TRAIN_PARAMS], float *const exp_avg[NGF_INFOINV_TRAIN_PARAMS],
+                               float *const exp_avg_sq[NGF_INFOINV_TRAIN_PARAMS], const int32_t step_count[NGF_INFOINV_TRAIN_PARAMS],
+                               const float lr[NGF_INFOINV_TRAIN_PARAMS], float beta1, float beta2, float eps, void *hip_stream);
 
 /* ---- UV-Mapping (NeuTex) colour path: UV-Mapping/model/model.py:27-59 ----------------------------------------
  * 29 nn.Linear layers in evaluation order, reference layouts (weight [out,in], bias [out], float32, device):

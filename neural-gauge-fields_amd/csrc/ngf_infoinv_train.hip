@@ -2,6 +2,7 @@
 // ngf_infoinv_train.hpp.  A translation unit of its own: ngf_field.hip and the ISA lint's compile of it stay as they were.
 #include "ngf_host.hpp"
 #include "ngf_infoinv_train.hpp"
+#include "ngf_infoinv_fused.hpp"
 
 using namespace ngf;
 
@@ -26,6 +27,13 @@ struct ngf_infoinv_trainer {
     bool packed = false;
     int64_t ticket = 0;                                // last forward's ticket (0 = none)
     bool have_grads = false;
+    // the fused step (ngf_infoinv_train_step_backward / _adam_all / _adam_ext / _get_grad)
+    float *f_rgb = nullptr, *f_depth = nullptr, *f_drgb = nullptr;     // [max_rays,3], [max_rays], [max_rays,3]
+    double *partb = nullptr;                           // bias partials [chunks][64]
+    float *exp_avg[NGF_INFOINV_TRAIN_PARAMS] = {}, *exp_avg_sq[NGF_INFOINV_TRAIN_PARAMS] = {};      // the caller's moments (set_moments)
+    bool have_moments = false;
+    bool have_fused = false;                           // a fused backward's gradients are in the trainer
+    bool planes_fixed = false;                         // ... the planes' as fixed point in gacc (one ray chunk); else as floats in grads[0..2]
 };
 
 namespace {
@@ -87,6 +95,100 @@ int ii_xty(ngf_infoinv_trainer *t, const float *X, const float *Y, int64_t rows_
     hipLaunchKernelGGL(ii_xty_reduce_kernel, dim3((M * (N + 1) + 255) / 256), dim3(256), 0, st, (const double *)t->part, chunks > 0 ? chunks : 1, M, N,
                        gw, gb, gw64);
     HIP_TRY(hipGetLastError());
+    return NGF_OK;
+}
+
+// the backward up to the per-sample deltas and the fixed-point plane sums (A.d_rgb set)
+int ii_backward_deltas(ngf_infoinv_trainer *t, hipStream_t st)
+{
+    IiArgs &A = t->A;
+    const int64_t n = A.n, pairs = n * (int64_t)A.S;
+    const unsigned rg = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(ii_composite_bwd_kernel, dim3(rg), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_color_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_density_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    // plane gradients: bound -> scale -> fixed-point scatter
+    hipLaunchKernelGGL(ii_bound_kernel, dim3(kIiBoundBlocks), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_scale_kernel, dim3(1), dim3(64), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    for (int p = 0; p < 3; ++p)
+        HIP_TRY(hipMemsetAsync(t->gacc[p], 0, (size_t)(A.tex[p].H + 2) * (A.tex[p].W + 2) * kIiC * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(ii_scatter_kernel<true>, dim3(grid_for(pairs * kIiDIn)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_scatter_kernel<false>, dim3(grid_for(pairs * kIiCF)), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    return NGF_OK;
+}
+
+// one weight-gradient product of the fused step on the matrix pipe (X: M delta rows, Y: N input rows) -> gw [M][N], gb [M], gw64 (nullable)
+int ii_mm(ngf_infoinv_trainer *t, const float *X, const float *Y, int64_t rows_cap, const int32_t *rows_dev, int M, int N, float *gw, float *gb,
+          double *gw64, bool accumulate, hipStream_t st)
+{
+    IiMm G{};
+    G.X = X; G.Y = Y; G.ld = t->cap; G.rows = rows_cap; G.rows_dev = rows_dev; G.M = M; G.N = N; G.part = t->part; G.partb = t->partb;
+    const int chunks = (int)((rows_cap + kIiMmChunk - 1) / kIiMmChunk);
+    const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
+    if ((int64_t)chunks * M * N > t->part_elems || M > kIiCH || chunks > 65535) return fail(NGF_E_ARG, "ngf_infoinv: product partials do not fit (internal)");
+    hipLaunchKernelGGL(ii_mm_kernel, dim3(tiles, chunks > 0 ? chunks : 1), dim3(256), 0, st, G);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ii_mm_reduce_kernel, dim3((M * N + M + 255) / 256), dim3(256), 0, st, (const double *)t->part, (const double *)t->partb, rows_cap,
+                       rows_dev, M, N, gw, gb, gw64, accumulate ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    return NGF_OK;
+}
+
+IiAdam ii_adam_args(int32_t step, float lr, float beta1, float beta2, float eps, float l1)
+{
+    IiAdam a;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.l1 = l1;
+    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    return a;
+}
+
+// grad NULL: the trainer's own gradients of the last fused backward (+ the L1 term on the planes); else the caller's tensors
+int ii_adam(ngf_infoinv_trainer *t, const float *const *grad, float *const *m, float *const *v, const int32_t *step_count, const float *lr, float beta1,
+            float beta2, float eps, float l1_weight, hipStream_t st)
+{
+    const ngf_infoinv_train_desc &d = t->desc;
+    const float *ps[NGF_INFOINV_TRAIN_PARAMS];
+    int64_t ns[NGF_INFOINV_TRAIN_PARAMS];
+    ii_params(d, ps, ns);
+    auto on = [&](int k) { return step_count[k] > 0 && (!grad || grad[k]); };
+    for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k)
+        if (on(k) && (!m[k] || !v[k])) return fail(NGF_E_ARG, "ngf_infoinv_train_adam: parameter %d has a gradient but no moments", k);
+    for (int p = 0; p < 3; ++p) {
+        if (!on(p)) continue;
+        const int H = d.plane_h[p], W = d.plane_w[p];
+        const IiAdam a = ii_adam_args(step_count[p], lr[p], beta1, beta2, eps, grad ? 0.0f : l1_weight / (float)((int64_t)kIiC * H * W));
+        const dim3 g(H * ((W + 63) / 64));
+        // a stale packed copy is simply rewritten; its zero border is written whenever the forward packs (t->packed unset)
+        if (!grad && t->planes_fixed)
+            hipLaunchKernelGGL(ii_adam_plane_kernel<true>, g, dim3(256), 0, st, d.plane[p], m[p], v[p], H, W, (const unsigned long long *)t->gacc[p],
+                               (const double *)t->A.bound, (const float *)nullptr, t->tex[p], a);
+        else
+            hipLaunchKernelGGL(ii_adam_plane_kernel<false>, g, dim3(256), 0, st, d.plane[p], m[p], v[p], H, W, (const unsigned long long *)nullptr,
+                               (const double *)nullptr, grad ? grad[p] : (const float *)t->grads[p], t->tex[p], a);
+        HIP_TRY(hipGetLastError());
+    }
+    IiAdamDense D;
+    int32_t at = 0;
+    for (int j = 0; j < kIiDense; ++j) {
+        const int k = 3 + j;
+        D.p[j] = (float *)ps[k]; D.m[j] = m[k]; D.v[j] = v[k]; D.g[j] = grad ? grad[k] : (const float *)t->grads[k];
+        D.begin[j] = at;
+        D.a[j] = ii_adam_args(step_count[k] > 0 ? step_count[k] : 1, lr[k], beta1, beta2, eps, 0.0f);
+        if (on(k)) at += (int32_t)ns[k];
+    }
+    D.begin[kIiDense] = at;
+    if (at > 0) {
+        hipLaunchKernelGGL(ii_adam_dense_kernel, dim3((at + 255) / 256), dim3(256), 0, st, D);
+        HIP_TRY(hipGetLastError());
+    }
     return NGF_OK;
 }
 
@@ -166,6 +268,9 @@ int ngf_infoinv_trainer_create(const ngf_infoinv_train_desc *desc, ngf_infoinv_t
     const int64_t chunks = (cap + kIiChunk - 1) / kIiChunk;
     t->part_elems = chunks * kIiCH * (kIiCIn + 1);
     if ((rc = ii_alloc_n(t, &t->part, t->part_elems))) return bail(rc);
+    if ((rc = ii_alloc_n(t, &t->f_rgb, 3 * nr)) || (rc = ii_alloc_n(t, &t->f_depth, nr)) || (rc = ii_alloc_n(t, &t->f_drgb, 3 * nr)) ||
+        (rc = ii_alloc_n(t, &t->partb, ((cap + kIiMmChunk - 1) / kIiMmChunk) * kIiCH)))
+        return bail(rc);
     for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k) {
         t->grad_elems[k] = ns[k];
         if ((rc = ii_alloc_n(t, &t->grads[k], ns[k]))) return bail(rc);
@@ -204,6 +309,7 @@ int ngf_infoinv_train_forward(ngf_infoinv_trainer *t, const float *rays, const f
     IiArgs &A = t->A;
     t->ticket = 0;                         // the buffers are overwritten from here on: no earlier ticket stays valid, even if this call fails
     t->have_grads = false;
+    t->have_fused = false;
     A.rays = rays; A.jitter = jitter; A.n = n; A.S = n_samples; A.white_bg = white_bg ? 1 : 0; A.infoinv = infoinv ? 1 : 0;
     A.rgb_out = rgb_map; A.depth_out = depth_map; A.d_rgb = nullptr;
     if (!t->packed) {
@@ -244,32 +350,16 @@ int ngf_infoinv_train_backward_grad(ngf_infoinv_trainer *t, int64_t ticket, cons
     hipStream_t st = (hipStream_t)hip_stream;
     IiArgs &A = t->A;
     A.d_rgb = d_rgb_map;
+    t->have_fused = false;
+    int rc;
+    if ((rc = ii_backward_deltas(t, st))) return rc;
     const int64_t n = A.n, pairs = n * (int64_t)A.S;
-    const unsigned rg = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ii_composite_bwd_kernel, dim3(rg), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_color_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_density_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    // plane gradients: bound -> scale -> fixed-point scatter -> reference layout
-    hipLaunchKernelGGL(ii_bound_kernel, dim3(kIiBoundBlocks), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_scale_kernel, dim3(1), dim3(64), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    for (int p = 0; p < 3; ++p)
-        HIP_TRY(hipMemsetAsync(t->gacc[p], 0, (size_t)(A.tex[p].H + 2) * (A.tex[p].W + 2) * kIiC * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(ii_scatter_kernel<true>, dim3(grid_for(pairs * kIiDIn)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_scatter_kernel<false>, dim3(grid_for(pairs * kIiCF)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
     for (int p = 0; p < 3; ++p) {
         hipLaunchKernelGGL(ii_plane_grad_kernel, dim3(grid_for((int64_t)kIiC * A.tex[p].H * A.tex[p].W)), dim3(256), 0, st,
                            (const unsigned long long *)t->gacc[p], (const double *)A.bound, A.tex[p].H, A.tex[p].W, t->grads[p]);
         HIP_TRY(hipGetLastError());
     }
     // weight gradients (which: 3..8 density mlp.{0,2,4}.{weight,bias}, 9 basis, 10..15 rgb mlp.{0,2,4}.{weight,bias})
-    int rc;
     const int32_t *na = A.offset + n;
     if ((rc = ii_xty(t, A.d_d1, A.d_in, pairs, nullptr, kIiDH, kIiDIn, t->grads[3], t->grads[4], nullptr, st)) ||
         (rc = ii_xty(t, A.d_d2, A.d_h1, pairs, nullptr, kIiDH, kIiDH, t->grads[5], t->grads[6], nullptr, st)) ||
@@ -293,6 +383,109 @@ int ngf_infoinv_train_get_grads(ngf_infoinv_trainer *t, float *const out[NGF_INF
     for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k)
         if (out[k]) HIP_TRY(hipMemcpyAsync(out[k], t->grads[k], (size_t)t->grad_elems[k] * sizeof(float), hipMemcpyDeviceToDevice, st));
     return NGF_OK;
+}
+
+// ---- the fused step -------------------------------------------------------------------------------------------------------------------------
+int ngf_infoinv_train_set_moments(ngf_infoinv_trainer *t, float *const exp_avg[NGF_INFOINV_TRAIN_PARAMS],
+                                  float *const exp_avg_sq[NGF_INFOINV_TRAIN_PARAMS])
+{
+    if (!t || !exp_avg || !exp_avg_sq) return fail(NGF_E_ARG, "ngf_infoinv_train_set_moments: null argument");
+    for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k)
+        if (!exp_avg[k] || !exp_avg_sq[k]) return fail(NGF_E_ARG, "ngf_infoinv_train_set_moments: the moments of parameter %d are NULL", k);
+    for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k) { t->exp_avg[k] = exp_avg[k]; t->exp_avg_sq[k] = exp_avg_sq[k]; }
+    t->have_moments = true;
+    return NGF_OK;
+}
+
+int ngf_infoinv_train_step_backward(ngf_infoinv_trainer *t, const float *rays, const float *rgb_train, const float *jitter, int64_t n, int32_t n_samples,
+                                    int32_t white_bg, int32_t infoinv, double *loss_out, void *hip_stream)
+{
+    if (!t || !rays || !rgb_train || !loss_out) return fail(NGF_E_ARG, "ngf_infoinv_train_step_backward: null argument");
+    if (n <= 0 || n >= (1ll << 31) / 3 || n_samples <= 0 || n_samples > t->max_samples)
+        return fail(NGF_E_ARG, "ngf_infoinv_train_step_backward: n = %lld, n_samples = %d outside the trainer's range (n_samples 1..%d)", (long long)n,
+                    n_samples, t->max_samples);
+    hipStream_t st = (hipStream_t)hip_stream;
+    DeviceScope ds(t->device);
+    int rc;
+    IiArgs &A = t->A;
+    const bool one = n <= t->max_rays;              // a batch of more rays than the trainer holds: ray chunks whose gradients add up
+    for (int64_t a = 0; a < n; a += t->max_rays) {
+        const int64_t nc = n - a < t->max_rays ? n - a : t->max_rays;
+        const bool acc = a > 0;
+        int64_t ticket = 0;
+        if ((rc = ngf_infoinv_train_forward(t, rays + a * 6, jitter ? jitter + a : nullptr, nc, n_samples, white_bg, infoinv, t->f_rgb, t->f_depth, &ticket,
+                                            hip_stream)))
+            return rc;
+        hipLaunchKernelGGL(ii_loss_kernel, dim3(1), dim3(1024), 0, st, (const float *)t->f_rgb, rgb_train + a * 3, nc * 3, n * 3, t->f_drgb, loss_out,
+                           acc ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        A.d_rgb = t->f_drgb;
+        if ((rc = ii_backward_deltas(t, st))) return rc;
+        if (!one)
+            for (int p = 0; p < 3; ++p) {
+                const unsigned g = grid_for((int64_t)kIiC * A.tex[p].H * A.tex[p].W);
+                if (acc)
+                    hipLaunchKernelGGL(ii_plane_grad_add_kernel, dim3(g), dim3(256), 0, st, (const unsigned long long *)t->gacc[p], (const double *)A.bound,
+                                       A.tex[p].H, A.tex[p].W, t->grads[p]);
+                else
+                    hipLaunchKernelGGL(ii_plane_grad_kernel, dim3(g), dim3(256), 0, st, (const unsigned long long *)t->gacc[p], (const double *)A.bound,
+                                       A.tex[p].H, A.tex[p].W, t->grads[p]);
+                HIP_TRY(hipGetLastError());
+            }
+        const int64_t pairs = nc * (int64_t)n_samples;
+        const int32_t *na = A.offset + nc;
+        if ((rc = ii_mm(t, A.d_d1, A.d_in, pairs, nullptr, kIiDH, kIiDIn, t->grads[3], t->grads[4], nullptr, acc, st)) ||
+            (rc = ii_mm(t, A.d_d2, A.d_h1, pairs, nullptr, kIiDH, kIiDH, t->grads[5], t->grads[6], nullptr, acc, st)) ||
+            (rc = ii_mm(t, A.dxs, A.d_h2, pairs, nullptr, 1, kIiDH, t->grads[7], t->grads[8], nullptr, acc, st)) ||
+            (rc = ii_mm(t, A.c_d1, A.c_in, pairs, na, kIiCH, kIiCIn, nullptr, t->grads[11], t->m64, acc, st)) ||
+            (rc = ii_mm(t, A.c_d2, A.c_h1, pairs, na, kIiCH, kIiCH, t->grads[12], t->grads[13], nullptr, acc, st)) ||
+            (rc = ii_mm(t, A.c_d3, A.c_h2, pairs, na, 3, kIiCH, t->grads[14], t->grads[15], nullptr, acc, st)))
+            return rc;
+    }
+    hipLaunchKernelGGL(ii_unfold_kernel, dim3((kIiCF * kIiCF + 255) / 256), dim3(256), 0, st, (const double *)t->m64, A.basis, A.w1, t->grads[10],
+                       t->grads[9]);
+    HIP_TRY(hipGetLastError());
+    t->ticket = 0;                   // the trainer's own d rgb_map went through: no autograd backward belongs to these forwards
+    t->have_grads = false;
+    t->have_fused = true;
+    t->planes_fixed = one;
+    return NGF_OK;
+}
+
+int ngf_infoinv_train_get_grad(ngf_infoinv_trainer *t, int32_t which, float *out, void *hip_stream)
+{
+    if (!t || !out || which < 0 || which >= NGF_INFOINV_TRAIN_PARAMS) return fail(NGF_E_ARG, "ngf_infoinv_train_get_grad: bad argument");
+    if (!t->have_fused) return fail(NGF_E_ARG, "ngf_infoinv_train_get_grad: no ngf_infoinv_train_step_backward since the last forward");
+    hipStream_t st = (hipStream_t)hip_stream;
+    DeviceScope ds(t->device);
+    if (which < 3 && t->planes_fixed) {
+        const Tex &x = t->A.tex[which];
+        hipLaunchKernelGGL(ii_plane_grad_kernel, dim3(grid_for((int64_t)kIiC * x.H * x.W)), dim3(256), 0, st, (const unsigned long long *)t->gacc[which],
+                           (const double *)t->A.bound, x.H, x.W, out);
+        HIP_TRY(hipGetLastError());
+        return NGF_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(out, t->grads[which], (size_t)t->grad_elems[which] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return NGF_OK;
+}
+
+int ngf_infoinv_train_adam_all(ngf_infoinv_trainer *t, const int32_t step_count[NGF_INFOINV_TRAIN_PARAMS], const float lr[NGF_INFOINV_TRAIN_PARAMS],
+                               float beta1, float beta2, float eps, float l1_weight, void *hip_stream)
+{
+    if (!t || !step_count || !lr) return fail(NGF_E_ARG, "ngf_infoinv_train_adam_all: null argument");
+    if (!t->have_moments) return fail(NGF_E_ARG, "ngf_infoinv_train_adam_all: no moments (ngf_infoinv_train_set_moments)");
+    if (!t->have_fused) return fail(NGF_E_ARG, "ngf_infoinv_train_adam_all: no ngf_infoinv_train_step_backward since the last forward");
+    DeviceScope ds(t->device);
+    return ii_adam(t, nullptr, t->exp_avg, t->exp_avg_sq, step_count, lr, beta1, beta2, eps, l1_weight, (hipStream_t)hip_stream);
+}
+
+int ngf_infoinv_train_adam_ext(ngf_infoinv_trainer *t, const float *const grad[NGF_INFOINV_TRAIN_PARAMS], float *const exp_avg[NGF_INFOINV_TRAIN_PARAMS],
+                               float *const exp_avg_sq[NGF_INFOINV_TRAIN_PARAMS], const int32_t step_count[NGF_INFOINV_TRAIN_PARAMS],
+                               const float lr[NGF_INFOINV_TRAIN_PARAMS], float beta1, float beta2, float eps, void *hip_stream)
+{
+    if (!t || !grad || !exp_avg || !exp_avg_sq || !step_count || !lr) return fail(NGF_E_ARG, "ngf_infoinv_train_adam_ext: null argument");
+    DeviceScope ds(t->device);
+    return ii_adam(t, grad, exp_avg, exp_avg_sq, step_count, lr, beta1, beta2, eps, 0.0f, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

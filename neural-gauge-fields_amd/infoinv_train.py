@@ -3,15 +3,20 @@ loop uses it (InfoInv/main.py:262-330) -- torch's loss, ``8e-5 * field.density_L
 
 ``InfoInvGrad`` is the device engine (include/ngf.h, ngf_infoinv_trainer_*): ``forward`` renders the batch with the trainer's kernels and keeps its
 per-sample buffers, ``backward`` takes d loss / d rgb_map and returns the gradients of the sixteen parameters in their reference layouts.
-``_InfoInvRender`` is the torch.autograd.Function around it; ``infoinv.TriPlane`` owns one engine per field when ``field.differentiable`` is set."""
+``_InfoInvRender`` is the torch.autograd.Function around it; ``infoinv.TriPlane`` owns one engine per field when ``field.differentiable`` is set.
+
+``Trainer`` is the fused form of the same loop body on the same engine: one call per iteration, the rgb loss and Adam inside the library, the weight
+gradients on the matrix pipe (ngf_infoinv_train_step_backward / _adam_all); ``fit`` is the lifecycle loop of InfoInv/main.py:243-336 around it."""
 from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
 
+L1_REG_WEIGHT = 8e-5            # InfoInv/main.py:259
 PARAM_NAMES = ('plane_xy', 'plane_yz', 'plane_xz',
                'density_decoder.mlp.0.weight', 'density_decoder.mlp.0.bias', 'density_decoder.mlp.2.weight', 'density_decoder.mlp.2.bias',
                'density_decoder.mlp.4.weight', 'density_decoder.mlp.4.bias',
@@ -47,6 +52,13 @@ def _bind(L):
     L.ngf_infoinv_train_backward_grad.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.ngf_infoinv_train_get_grads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.ngf_infoinv_train_params_changed.argtypes = [C.c_void_p]
+    L.ngf_infoinv_train_step_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                  C.c_void_p]
+    L.ngf_infoinv_train_set_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ngf_infoinv_train_adam_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
+    L.ngf_infoinv_train_get_grad.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ngf_infoinv_train_adam_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                             C.c_void_p]
     if L.ngf_sizeof_infoinv_train_desc() != C.sizeof(InfoInvTrainDesc):
         raise RuntimeError("libngf_hip.so ABI mismatch (ngf_infoinv_train_desc layout)")
     L._ngf_infoinv_bound = True
@@ -114,6 +126,11 @@ class InfoInvGrad:
         self._h = out
         self.key = _field_key(field, self.params)
         self._versions = None                   # the first forward packs the planes
+        self.repacks = 0                        # how often the packed planes were marked stale (ngf_infoinv_train_params_changed)
+        self._moments_owner = None              # the Trainer whose Adam moments the handle holds
+        self.adam_ext = self.L.ngf_infoinv_train_adam_ext      # what ngf_amd.optim.Adam calls for this engine's parameters
+        from . import optim
+        optim.register(field, self.params)      # ngf_amd.optim.Adam finds the engine behind a parameter (fused update, no re-pack)
 
     @property
     def bytes(self) -> int:
@@ -133,14 +150,19 @@ class InfoInvGrad:
         except Exception:
             pass
 
-    def forward(self, rays, jitter, S, white_bg, infoinv):
-        """-> (rgb_map [n,3], depth_map [n], ticket).  The packed planes follow torch's in-place version counters (optimizer.step(),
-        load_state_dict); ``field.invalidate()`` marks them stale for writes that bypass the counters."""
+    def sync_planes(self):
+        """The packed planes follow torch's in-place version counters (optimizer.step(), load_state_dict); ``field.invalidate()`` marks them
+        stale for writes that bypass the counters.  The library's own Adam writes the packed copies itself and bumps nothing."""
         v = tuple(int(p._version) for p in self.params[:3])
         if v != self._versions or getattr(self.field, "_grad_stale", False):
             _lib.check(self.L.ngf_infoinv_train_params_changed(self._h))
+            self.repacks += 1
             self._versions = v
             self.field._grad_stale = False
+
+    def forward(self, rays, jitter, S, white_bg, infoinv):
+        """-> (rgb_map [n,3], depth_map [n], ticket); see ``sync_planes`` for when the planes are packed again."""
+        self.sync_planes()
         n = rays.shape[0]
         rgb = torch.empty((n, 3), device=self.dev, dtype=torch.float32)
         depth = torch.empty((n,), device=self.dev, dtype=torch.float32)
@@ -197,3 +219,197 @@ class _InfoInvRender(torch.autograd.Function):
             if grads is None:
                 raise RuntimeError(_lib.lib().ngf_last_error().decode())
         return (None,) * 7 + tuple(grads)
+
+
+def _max_rays(field, S):
+    """The autograd path's rule (infoinv.TriPlane._render_train_infoinv): at most ``field.grad_max_pairs`` (ray, sample) pairs per ray chunk."""
+    return max(1, max(int(getattr(field, 'grad_max_pairs', 1 << 22)), int(S)) // int(S))
+
+
+class Trainer:
+    """Adam state + the fused training step of one InfoInv field (the body of InfoInv/main.py:262-330):
+
+        output = field(rays_train, is_train=True, white_bg=white_bg, N_samples=nSamples, infoinv=infoinv)
+        total_loss = mean((rgb_map - rgb_train)**2) + L1_reg_weight * field.density_L1()
+        optimizer.zero_grad(); total_loss.backward(); optimizer.step()          # Adam(get_optparam_groups, betas=(0.9, 0.99))
+        for g in optimizer.param_groups: g['lr'] *= lr_factor
+
+    ``step(rays_train, rgb_train)`` does that in two library calls on the field's differentiable engine (the autograd path keeps working on the
+    same field); the nn.Parameters are updated in place.  Arguments as ``ngf_amd.train.Trainer``; learning rates per InfoInv/models/Field.py:27-37:
+    the three planes at ``lr_init``, both decoders at ``lr_basis``.  There is no CPU path."""
+
+    def __init__(self, field, batch_size=4096, max_samples=None, lr_init=0.02, lr_basis=1e-3, lr_decay_iters=-1, lr_decay_target_ratio=0.1,
+                 n_iters=30000, L1_reg_weight=L1_REG_WEIGHT, betas=(0.9, 0.99), eps=1e-8, frozen=(), state_from=None):
+        self.field = field
+        self.dev = torch.device(field.device)
+        if self.dev.type != "cuda":
+            raise RuntimeError("ngf_amd.infoinv_train.Trainer runs on the GPU only (device='cuda'); there is no CPU path")
+        self.L = _lib.lib()
+        _bind(self.L)
+        self.params = train_params(field)
+        self.exp_avg = [torch.zeros_like(p) for p in self.params]
+        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+        self.steps = [0] * NPARAMS                  # torch.optim.Adam keeps one step counter per parameter
+        self.frozen = set(PARAM_NAMES.index(k) if isinstance(k, str) else int(k) for k in frozen)
+        self.lr = [lr_init] * 3 + [lr_basis] * (NPARAMS - 3)
+        self.lr_factor = lr_decay_target_ratio ** (1 / (lr_decay_iters if lr_decay_iters > 0 else n_iters))
+        self.betas, self.eps, self.l1 = betas, eps, L1_reg_weight
+        self.batch_size = int(batch_size)
+        self.max_samples = int(max_samples if max_samples is not None else field.nSamples)
+        if state_from is not None:                  # carry the optimiser state of parameters that kept their shape
+            for k in range(NPARAMS):
+                if state_from.exp_avg[k].shape == self.exp_avg[k].shape:
+                    self.exp_avg[k].copy_(state_from.exp_avg[k])
+                    self.exp_avg_sq[k].copy_(state_from.exp_avg_sq[k])
+                    self.steps[k] = state_from.steps[k]
+            self.lr = list(state_from.lr)
+        self._loss = torch.zeros((2,), dtype=torch.float64, device=self.dev)      # [sum of squared residuals, their mean]
+        self._eng = None
+        self._have_grads = False
+        self._shape_key = _field_key(field, self.params)
+        self._engine(self.batch_size, self.max_samples)
+
+    def _engine(self, n, S):
+        """The field's engine, sized for one ray chunk of the batch; this trainer's moments are the ones its handle updates."""
+        f = self.field
+        per = _max_rays(f, S)
+        eng = getattr(f, '_ii_engine', None)
+        if eng is not None and eng._h is not None and n > per and eng.max_rays > per:
+            f.release_grad_engine()                 # built for more pairs than grad_max_pairs allows now: the library chunks by the engine's size
+        eng = f._infoinv_grad_engine(min(int(n), per), S)
+        if eng is not self._eng or eng._moments_owner is not self:
+            m = (C.c_void_p * NPARAMS)(*[t.data_ptr() for t in self.exp_avg])
+            v = (C.c_void_p * NPARAMS)(*[t.data_ptr() for t in self.exp_avg_sq])
+            _lib.check(self.L.ngf_infoinv_train_set_moments(eng._h, m, v))
+            eng._moments_owner = self
+            if eng is not self._eng:
+                self._have_grads = False
+            self._eng = eng
+        return eng
+
+    def release(self):
+        """Free the engine's device buffers if this trainer's engine is still the field's; the moments stay (``state_from=``)."""
+        eng, self._eng = getattr(self, "_eng", None), None
+        if eng is not None and getattr(self.field, '_ii_engine', None) is eng:
+            self.field.release_grad_engine()
+
+    def params_changed(self):
+        """Tell the trainer that plane values were written by something that bumps no version counter (``.data`` writes, raw pointers): the
+        channel-last copies are rebuilt at the next ``backward``.  In-place torch ops and ``load_state_dict`` are seen without it."""
+        self.field._grad_stale = True
+
+    @torch.no_grad()
+    def backward(self, rays_train, rgb_train, N_samples=-1, white_bg=True, infoinv=True, jitter=None, coin=None, keep_loss=False):
+        """forward(is_train=True) + backward of the rgb MSE; returns the rgb loss as a 0-dim float64 device tensor.  ``jitter`` [n] and ``coin``
+        (a float in [0,1)) replace torch.rand_like / torch.rand((1,)) for parity tests.  A batch of more than ``field.grad_max_pairs`` pairs is
+        worked through in ray chunks whose gradients add up; nothing is truncated.
+
+        ALIASING: by default the returned tensor is a VIEW of the trainer's persistent loss buffer -- the next ``backward`` overwrites it in
+        place.  Read it (``.item()``) before the next step, or pass ``keep_loss=True`` for a fresh tensor per step."""
+        if _field_key(self.field, train_params(self.field)) != self._shape_key:
+            raise RuntimeError("the field's parameters, alpha mask or geometry were re-allocated (load / a new mask): build a new Trainer")
+        rays = rays_train.to(device=self.dev, dtype=torch.float32).contiguous()
+        tgt = rgb_train.to(device=self.dev, dtype=torch.float32).contiguous()
+        n = rays.shape[0]
+        if rays.dim() != 2 or rays.shape[1] != 6 or tuple(tgt.shape) != (n, 3) or n == 0:
+            raise ValueError(f"rays_train must be [n,6] and rgb_train [n,3] with n > 0, got {tuple(rays.shape)} / {tuple(tgt.shape)}")
+        S = int(N_samples) if N_samples > 0 else int(self.field.nSamples)
+        if jitter is None:
+            jitter = torch.rand((n,), device=self.dev)                 # FieldBase.py:128-130
+        jitter = jitter.to(device=self.dev, dtype=torch.float32).reshape(n).contiguous()
+        white = bool(white_bg or ((float(torch.rand((1,))) if coin is None else float(coin)) < 0.5))      # FieldBase.py:270
+        eng = self._engine(n, S)
+        eng.sync_planes()
+        with torch.cuda.device(eng.dev):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(self.L.ngf_infoinv_train_step_backward(eng._h, rays.data_ptr(), tgt.data_ptr(), jitter.data_ptr(), n, S, int(white),
+                                                              int(bool(infoinv)), self._loss.data_ptr(), st))
+        self._have_grads = True
+        return self._loss[1].clone() if keep_loss else self._loss[1]
+
+    @torch.no_grad()
+    def gradient(self, which) -> torch.Tensor:
+        """The gradient of one parameter (index or state_dict name) in its reference layout, after ``backward``.  Planes exclude the L1 term
+        (it is added inside the Adam kernel)."""
+        k = PARAM_NAMES.index(which) if isinstance(which, str) else int(which)
+        if self._eng is None or self._eng._h is None or not self._have_grads:
+            raise RuntimeError("gradient() needs a backward() first")
+        out = torch.empty_like(self.params[k])
+        with torch.cuda.device(self._eng.dev):
+            _lib.check(self.L.ngf_infoinv_train_get_grad(self._eng._h, k, out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out
+
+    @torch.no_grad()
+    def optimizer_step(self):
+        """optimizer.step() + the lr decay of main.py:298-299.  Frozen parameters get no update and their step counters stay.  One update per
+        ``backward``.  A differentiable forward of the same field under autograd between ``backward`` and this call goes through the same
+        engine and retires the gradients: the library then refuses the update (a RuntimeError from this call) -- run ``backward`` again."""
+        eng = self._eng
+        if eng is None or eng._h is None or not self._have_grads or getattr(self.field, '_ii_engine', None) is not eng:
+            raise RuntimeError("optimizer_step() needs a backward() first")
+        if eng._moments_owner is not self:
+            raise RuntimeError("another Trainer used this field's engine since the backward: run backward() again")
+        counts = (C.c_int32 * NPARAMS)()
+        for k in range(NPARAMS):
+            if k in self.frozen:
+                continue                              # count 0 = skipped
+            self.steps[k] += 1
+            counts[k] = self.steps[k]
+        lrs = (C.c_float * NPARAMS)(*[float(x) for x in self.lr])
+        with torch.cuda.device(eng.dev):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(self.L.ngf_infoinv_train_adam_all(eng._h, counts, lrs, float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                                                         float(self.l1), st))
+        self._have_grads = False         # one update per backward: a second optimizer_step() raises instead of applying the gradients again
+        self.field.invalidate()          # parameters changed behind torch's back: the eval image is re-packed on the next render ...
+        self.field._grad_stale = False   # ... but the engine's packed planes were written by the Adam pass itself
+        self.lr = [x * self.lr_factor for x in self.lr]
+
+    def step(self, rays_train, rgb_train, N_samples=-1, white_bg=True, infoinv=True, jitter=None, coin=None, keep_loss=False):
+        """One iteration of main.py:262-330.  Returns the rgb loss (0-dim float64 device tensor; ``.item()`` for PSNR) -- a view of the trainer's
+        loss buffer that the next step overwrites unless ``keep_loss=True`` (see ``backward``)."""
+        loss = self.backward(rays_train, rgb_train, N_samples, white_bg, infoinv, jitter, coin, keep_loss=keep_loss)
+        self.optimizer_step()
+        return loss
+
+
+def fit(field, allrays, allrgbs, args, white_bg=True, infoinv=True, on_iteration=None):
+    """The optimisation loop of InfoInv/main.py:243-336 on top of ``Trainer`` -- no dataset, logging or checkpoint code (those stay with the
+    caller; ``on_iteration(iteration, rgb_loss)`` is the hook for them).  The InfoInv loop has no ``shrink`` and no up-sampling.
+
+    ``args``: the reference's namespace: batch_size, n_iters, lr_init, lr_basis, lr_decay_iters, lr_decay_target_ratio, update_AlphaMask_list,
+    nSamples, step_ratio.  Returns the per-iteration PSNR list."""
+    from . import geometry
+    from .train import SimpleSampler
+    dev = torch.device(field.device)
+    mask_list = list(args.update_AlphaMask_list or [])
+    nSamples = min(int(args.nSamples), geometry.cal_n_samples([int(v) for v in field.gridSize], args.step_ratio))
+    allrays, allrgbs = field.filtering_rays(allrays, allrgbs, bbox_only=True)
+    sampler = SimpleSampler(allrays.shape[0], args.batch_size)
+
+    def new_trainer(state_from=None, l1=L1_REG_WEIGHT):
+        return Trainer(field, batch_size=args.batch_size, max_samples=nSamples, lr_init=args.lr_init, lr_basis=args.lr_basis,
+                       lr_decay_iters=args.lr_decay_iters, lr_decay_target_ratio=args.lr_decay_target_ratio, n_iters=args.n_iters,
+                       L1_reg_weight=l1, state_from=state_from)
+
+    l1 = L1_REG_WEIGHT
+    trainer = new_trainer()
+    PSNRs = []
+    for iteration in range(args.n_iters):
+        ids = sampler.nextids()
+        rays_train, rgb_train = allrays[ids].to(dev), allrgbs[ids].to(dev)
+        rgb_loss = trainer.step(rays_train, rgb_train, N_samples=nSamples, white_bg=white_bg, infoinv=infoinv).item()
+        PSNRs.append(-10.0 * np.log(rgb_loss) / np.log(10.0))
+        if on_iteration is not None:
+            on_iteration(iteration, rgb_loss)
+        if iteration in mask_list:
+            field.updateAlphaMask((256, 256, 256), infoinv=infoinv)
+            if iteration == mask_list[0]:
+                l1 = 4e-5                                                    # main.py:328
+                allrays, allrgbs = field.filtering_rays(allrays, allrgbs)
+                sampler = SimpleSampler(allrgbs.shape[0], args.batch_size)
+            old = trainer
+            trainer = new_trainer(state_from=old, l1=l1)                     # new mask -> new device image
+            old.release()
+    trainer.release()
+    return PSNRs

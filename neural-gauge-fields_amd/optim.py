@@ -13,6 +13,8 @@ the differentiable forward's channel-last copy of the plane.  What leaves the st
 launches over 52 MB of parameters and, at the next ``field(rays, is_train=True)``, the re-pack of three planes (torch's in-place update makes the
 copies stale).  Parameters that do not belong to a field with a live differentiable engine -- and groups that ask for amsgrad, weight decay,
 maximize, capturable or differentiable -- take torch's own path (``super().step()``), so the class is a superset, not a special case.
+An InfoInv field (``ngf_amd.infoinv.TriPlane`` with ``differentiable = True``) is taken the same way: its sixteen parameters go through
+``ngf_infoinv_train_adam_ext`` once its differentiable engine is live, and the next differentiable forward packs nothing.
 There is no CPU path for the fused part; on CPU tensors everything is torch's."""
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ import torch
 from . import _lib
 
 # id(parameter) -> (weak parameter, weak field, index in train.PARAM_NAMES); filled by train.RenderGrad when a field's differentiable engine is
-# built.  (Keyed by id: a tensor cannot key a WeakKeyDictionary -- its == is elementwise.)
+# built (and by infoinv_train.InfoInvGrad, with the index in infoinv_train.PARAM_NAMES).  (Keyed by id: a tensor cannot key a WeakKeyDictionary -- its == is elementwise.)
 _OWNERS = {}
 
 
@@ -49,7 +51,7 @@ class Adam(torch.optim.Adam):
                 if own is None or own[0]() is not p:
                     continue
                 field, k = own[1](), own[2]
-                eng = None if field is None else getattr(field, '_grad_engine', None)
+                eng = None if field is None else (getattr(field, '_grad_engine', None) or getattr(field, '_ii_engine', None))
                 if eng is None or eng._h is None or eng.params[k] is not p:
                     continue
                 g_ = p.grad
@@ -66,8 +68,9 @@ class Adam(torch.optim.Adam):
                 loss = closure()
         taken = []
         for field, eng, items in self._plan():
-            grads, m, v = (C.c_void_p * 15)(), (C.c_void_p * 15)(), (C.c_void_p * 15)()
-            counts, lrs = (C.c_int32 * 15)(), (C.c_float * 15)()
+            np_ = len(eng.params)                  # the arrays of the engine's own call (eng.adam_ext): 15 TriPlane, 16 InfoInv
+            grads, m, v = (C.c_void_p * np_)(), (C.c_void_p * np_)(), (C.c_void_p * np_)()
+            counts, lrs = (C.c_int32 * np_)(), (C.c_float * np_)()
             beta = None
             ok = True
             for g, p, k in items:          # one call takes one pair of betas / eps: the reference's groups share them (main.py:242)
@@ -96,8 +99,7 @@ class Adam(torch.optim.Adam):
                 grads[k], m[k], v[k] = p.grad.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr()
                 taken.append(p)
             with torch.cuda.device(eng.dev):
-                _lib.check(eng.L.ngf_train_adam_ext(eng._h, grads, m, v, counts, lrs, beta[0], beta[1], beta[2],
-                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                _lib.check(eng.adam_ext(eng._h, grads, m, v, counts, lrs, beta[0], beta[1], beta[2], C.c_void_p(torch.cuda.current_stream().cuda_stream)))
             # the parameters changed behind torch's version counters: the eval image is rebuilt at the next render; the differentiable
             # engine's packed planes were written by the call itself and stay current
             field._handle_key = None

@@ -404,6 +404,7 @@ class RenderGrad:
         self._versions = tuple(int(p._version) for p in self.params[:6])
         self._last_active, self._last_n = 0, 0
         self._active_dev = torch.zeros((1,), dtype=torch.int32, device=self.dev)
+        self.adam_ext = self.L.ngf_train_adam_ext       # what ngf_amd.optim.Adam calls for this engine's parameters
         from . import optim
         optim.register(field, self.params)          # ngf_amd.optim.Adam finds the engine behind a parameter (fused update, no re-pack)
 
