@@ -471,6 +471,11 @@ int ngf_debug_xcd_histogram(unsigned *out8, int32_t workgroups, void *hip_stream
  * tiles.  Returns the number of segments (1..4); unused entries are zeroed.  (Why: a persistent grid ends when its last wave does -- narrow
  * tiles for the last rays let the waves run dry together.) */
 int ngf_debug_tile_plan(int64_t n, int32_t wide, int64_t resident, int32_t tail16, int64_t *seg_rays, int32_t *seg_shift);
+/* Floats a handle allocates for one packed plane of H x W texels with nc channels (host arithmetic only, no GPU): (H + 2)(W + 2) nc in the
+ * one-row form, twice that in the row-pair form (pair != 0: padded texel (x, y) holds its own channels, then those of (x, y + 1); the march's baked
+ * density and gauge planes of levels 2 and 3).  Knob "pairpack" = 0 at ngf_field_create keeps the one-row form for A/B runs (libngf_hip_exp.so only;
+ * the product library refuses it).  -1 for a size below 1. */
+int64_t ngf_debug_packed_plane_floats(int32_t H, int32_t W, int32_t nc, int32_t pair);
 /* ---- the UV-Mapping (NeuTex) training step: UV-Mapping/model/model.py:27-59, 300-356 ---------------------------------------------------------
  * Replaces NeuTex.forward under autograd (color, transmittance, uv, the blend weights, the sample positions) and its backward, for a caller that
  * owns the losses and the optimiser (ngf_amd.uvmapping.NeuTex with `differentiable = True`).  Additive to ABI 5.  The 29 render layers are the

@@ -24,7 +24,7 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_uv_create", "ngf_uv_destroy", "ngf_uv_render", "ngf_uv_render_batch", "ngf_field_alpha", "ngf_field_ray_filter",
            "ngf_eval_workspace_bytes", "ngf_eval_frame_u8", "ngf_eval_depth_range", "ngf_eval_depth_colormap", "ngf_eval_mse",
            "ngf_eval_ssim", "ngf_trainer_create", "ngf_trainer_destroy", "ngf_trainer_bytes", "ngf_sizeof_train_desc", "ngf_train_backward", "ngf_train_backward2",
-           "ngf_train_forward", "ngf_train_backward_grad", "ngf_train_get_grad", "ngf_train_get_active", "ngf_train_overflow_count", "ngf_train_adam", "ngf_train_adam_all", "ngf_train_adam_ext", "ngf_train_get_grads", "ngf_train_params_changed", "ngf_train_debug_sections", "ngf_resize_bilinear", "ngf_uv_set_texture", "ngf_uv_texture_edit", "ngf_field_alpha_mask_build", "ngf_pack_mask_bits", "ngf_debug_set", "ngf_debug_get", "ngf_debug_dirty_lds", "ngf_debug_xcd_histogram", "ngf_debug_tile_plan", "ngf_debug_tile_order", "ngf_planes_l1", "ngf_planes_l1_backward", "ngf_pool_trim", "ngf_pool_set_limit", "ngf_pool_bytes",
+           "ngf_train_forward", "ngf_train_backward_grad", "ngf_train_get_grad", "ngf_train_get_active", "ngf_train_overflow_count", "ngf_train_adam", "ngf_train_adam_all", "ngf_train_adam_ext", "ngf_train_get_grads", "ngf_train_params_changed", "ngf_train_debug_sections", "ngf_resize_bilinear", "ngf_uv_set_texture", "ngf_uv_texture_edit", "ngf_field_alpha_mask_build", "ngf_pack_mask_bits", "ngf_debug_set", "ngf_debug_get", "ngf_debug_dirty_lds", "ngf_debug_xcd_histogram", "ngf_debug_tile_plan", "ngf_debug_packed_plane_floats", "ngf_debug_tile_order", "ngf_planes_l1", "ngf_planes_l1_backward", "ngf_pool_trim", "ngf_pool_set_limit", "ngf_pool_bytes",
            "ngf_infoinv_trainer_create", "ngf_infoinv_trainer_destroy", "ngf_infoinv_trainer_bytes", "ngf_sizeof_infoinv_train_desc",
            "ngf_infoinv_train_forward", "ngf_infoinv_train_backward_grad", "ngf_infoinv_train_get_grads", "ngf_infoinv_train_params_changed",
            "ngf_infoinv_train_step_backward", "ngf_infoinv_train_set_moments", "ngf_infoinv_train_adam_all", "ngf_infoinv_train_get_grad",
@@ -127,6 +127,8 @@ def _load(path):
         L.ngf_debug_dirty_lds.argtypes = [C.c_void_p]
         L.ngf_debug_xcd_histogram.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.ngf_debug_tile_plan.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.ngf_debug_packed_plane_floats.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.ngf_debug_packed_plane_floats.restype = C.c_int64
         L.ngf_pool_set_limit.argtypes = [C.c_int64]
         L.ngf_pool_bytes.argtypes = [C.c_int32]
         L.ngf_pool_bytes.restype = C.c_int64
@@ -197,6 +199,6 @@ def knobs_from_env():
     if any(os.environ.get("NGF_" + k.upper()) not in (None, "", "-1") for k in ("waves", "nstep", "profile", "kernel", "stage")):
         _LIB = _load(SO_PATH_EXP)          # these knobs select experiment kernels: the whole script runs on libngf_hip_exp.so
     L = lib()
-    for k in ("tile_w", "split", "waves", "nstep", "profile", "ablate", "uv_tiles", "kernel", "stage", "xcd", "grid", "tail", "ord_rows", "ord_px", "train_dwg"):
+    for k in ("tile_w", "split", "waves", "nstep", "profile", "ablate", "uv_tiles", "kernel", "stage", "xcd", "grid", "tail", "ord_rows", "ord_px", "train_dwg", "pairpack"):
         v = os.environ.get("NGF_" + k.upper())
         check(L.ngf_debug_set(k.encode(), int(v) if v not in (None, "") else -1))

@@ -14,6 +14,7 @@
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));      // a 16-byte load from an 8-byte aligned address (row-pair density cells)
 
 namespace ngf {
 
@@ -24,6 +25,10 @@ constexpr int kViewFeat = 16;       // [d(3), sin(6), cos(6), 0]
 
 // A packed texture: channel-last texels with a one-texel zero border (zeros padding of
 // grid_sample becomes an in-bounds read of a zero texel).  p points at padded texel (0,0).
+// Row-pair form (the march's baked density planes and, with them, the gauge planes -- levels 2 and 3): padded texel (x, y) holds its own channels
+// followed by those of (x, y + 1), so the four taps of a bilinear cell are ONE contiguous run at texel index idx -- 16 bytes for a 1-channel plane,
+// 32 for a 2-channel one -- instead of two row halves a padded row apart (pack kernels: ngf_field.hip; readers: ngf_render.hpp).  The descriptor is
+// the same: idx and stride count texels, only the bytes per texel double.  Padded rows 0 .. H + 1 all exist; the last one pairs with zeros.
 struct Tex {
     const float *p;
     int32_t W, H;       // un-padded size; u indexes W, v indexes H
@@ -87,6 +92,9 @@ struct RenderArgs {
     int32_t ablate;        // debug instantiations only (render_kernel<.., DBG = true>): 32 no early termination, 64 no empty-iteration skip, 128 no empty-space skipping through the mask's block image -- both
                            // EXACT (A/B timing and the bit-identity tests).  Round 1-2's bits 1 / 2 / 4 / 16 (skip collect, skip layers 2-3, cached
                            // gathers, wave priority) produced wrong images and are gone; the trainer keeps its own bits (ngf_train.hpp)
+    int32_t gauge_same;    // the three gauge planes are square and of one size (host, at create): triplane_gauge sets a cell axis up once per coordinate
+    int32_t pairpack;      // dens (1-channel) and gau are in the row-pair form (struct Tex).  Always 1 for a handle with NGF_F_BAKE_DENSITY; only the
+                           // experiment library reads it in a kernel (ngf_debug_set("pairpack", 0) at create: the one-row layout, for A/B runs)
     float a0[3], a1[3], inv[3];
     float near_, far_, step, dscale, thr;
     Tex dens[3];           // TriPlane: 16-ch (faithful) or 1-ch (baked) density texels
@@ -261,6 +269,42 @@ __device__ __forceinline__ Bil bil_setup(float u, float v, const Tex &t)
     b.cx = (int)cx + 1;
     b.cy = (int)cy + 1;
     b.idx = (int)__umul24((unsigned)b.cy, (unsigned)t.stride) + b.cx;      // both factors < 2^24: the full-rate 24-bit multiply
+    b.w00 = wx0 * wy0;
+    b.w10 = wx1 * wy0;
+    b.w01 = wx0 * wy1;
+    b.w11 = wx1 * wy1;
+    return b;
+}
+
+// One axis of a bilinear cell: what bil_setup computes from one coordinate and one size, with its operations (hence its bits).
+struct BilAxis {
+    float w0, w1;        // 1 - frac, frac
+    int32_t c;           // padded index of the lower tap
+    bool in;             // the clamp left the cell index alone
+};
+__device__ __forceinline__ BilAxis bil_axis(float u, float fw)
+{
+    const float px = ((u + 1.0f) / 2.0f) * fw;
+    const float fx = floorf(px);
+    BilAxis a;
+    a.w1 = px - fx; a.w0 = 1.0f - a.w1;
+    const float cx = __builtin_amdgcn_fmed3f(fx, -1.0f, fw);
+    a.in = cx == fx;
+#ifdef NGF_EXP_NOMASK
+    a.in = true;
+#endif
+    a.c = (int)cx + 1;
+    return a;
+}
+// The cell of (x axis, y axis): bil_setup<true> of the two coordinates on a plane of that size.
+__device__ __forceinline__ Bil bil_from_axes(const BilAxis &x, const BilAxis &y, int32_t stride)
+{
+    const bool in = x.in & y.in;
+    Bil b;
+    b.wx1 = x.w1; b.wy1 = y.w1; b.in = in ? 1 : 0;
+    const float wx0 = in ? x.w0 : 0.0f, wx1 = in ? x.w1 : 0.0f, wy0 = in ? y.w0 : 0.0f, wy1 = in ? y.w1 : 0.0f;
+    b.cx = x.c; b.cy = y.c;
+    b.idx = (int)__umul24((unsigned)y.c, (unsigned)stride) + x.c;
     b.w00 = wx0 * wy0;
     b.w10 = wx1 * wy0;
     b.w01 = wx0 * wy1;

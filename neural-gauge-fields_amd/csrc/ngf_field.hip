@@ -31,7 +31,7 @@ int ngf::fail(int code, const char *fmt, ...)
 }
 
 static std::atomic<int> g_knob[ngf::KNOB_COUNT];
-static const char *const g_knob_name[ngf::KNOB_COUNT] = {"tile_w", "split", "waves", "nstep", "profile", "ablate", "uv_tiles", "kernel", "stage", "poison", "grid", "xcd", "tail", "ord_rows", "ord_px", "train_dwg"};
+static const char *const g_knob_name[ngf::KNOB_COUNT] = {"tile_w", "split", "waves", "nstep", "profile", "ablate", "uv_tiles", "kernel", "stage", "poison", "grid", "xcd", "tail", "ord_rows", "ord_px", "train_dwg", "pairpack"};
 static bool g_knob_init = [] { for (auto &k : g_knob) k.store(-1); return true; }();
 
 int ngf::knob(int id) { return g_knob[id].load(std::memory_order_relaxed); }
@@ -167,7 +167,9 @@ static inline void field_use(const ngf_field *f, hipStream_t st)
 // ---- packing kernels -----------------------------------------------------------------------------
 // NCHW [C,H,W] channels [c0,c0+nc) -> zero-bordered channel-last [(H+2)][(W+2)][nc]
 // perm = 1: the colour channels in the order of infoinv_split_channel (InfoInv NGF_F_SPLIT_BF16, nc = 72)
-__global__ void pack_plane_kernel(const float *__restrict__ src, int H, int W, int c0, int nc, float *__restrict__ dst, int perm = 0)
+// pair = 1: the row-pair form (struct Tex, ngf_device.hpp) [(H+2)][(W+2)][2][nc]: slot 0 of padded texel (x, y) holds (x, y), slot 1 holds (x, y + 1) --
+// every value is stored twice, as its own texel's slot 0 and as slot 1 of the texel above; the last padded row pairs with zeros.
+__global__ void pack_plane_kernel(const float *__restrict__ src, int H, int W, int c0, int nc, float *__restrict__ dst, int perm = 0, int pair = 0)
 {
     const size_t total = (size_t)(H + 2) * (W + 2) * nc;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -176,8 +178,23 @@ __global__ void pack_plane_kernel(const float *__restrict__ src, int H, int W, i
         const int x = (int)(tx % (W + 2)), y = (int)(tx / (W + 2));
         float v = 0.0f;
         if (x >= 1 && x <= W && y >= 1 && y <= H) v = src[((size_t)(c0 + (perm ? infoinv_split_channel(c) : c)) * H + (y - 1)) * W + (x - 1)];
-        dst[i] = v;
+        if (pair) {
+            dst[tx * 2 * nc + c] = v;
+            if (y >= 1) dst[((tx - (W + 2)) * 2 + 1) * nc + c] = v;
+            if (y == H + 1) dst[(tx * 2 + 1) * nc + c] = 0.0f;
+        } else dst[i] = v;
     }
+}
+
+// Rows of a packed plane of H rows as allocated: the padded rows 0 .. H + 1, in both forms (the row-pair form doubles the texel, not the rows).  The march's
+// cells start at padded (cx, cy) in [0, W] x [0, H] (bil_setup) and read texels idx, idx + 1 of row cy -- and, in the one-row form, of row cy + 1.
+static inline size_t packed_plane_floats(int H, int W, int nc, bool pair) { return (size_t)(H + 2) * (W + 2) * nc * (pair ? 2 : 1); }
+
+// tests: the size arithmetic above
+extern "C" int64_t ngf_debug_packed_plane_floats(int32_t H, int32_t W, int32_t nc, int32_t pair)
+{
+    if (H < 1 || W < 1 || nc < 1) return -1;
+    return (int64_t)packed_plane_floats(H, W, nc, pair != 0);
 }
 
 // Alpha mask, second image (round 6): per trilinear cell -- base corner (z, y, x) in -1 .. D-1 / H-1 / W-1 -- one byte with the bits of its 8 corners
@@ -235,7 +252,7 @@ __global__ void __launch_bounds__(256) mask_block_clear_kernel(const uint8_t *__
 
 // density_decoder Linear(48,1) pre-composed with the density channels of one plane (fp64 accumulate)
 __global__ void bake_density_kernel(const float *__restrict__ src, int H, int W, int nc, const float *__restrict__ wd,
-                                    float *__restrict__ dst)
+                                    float *__restrict__ dst, int pair)
 {
     const size_t total = (size_t)(H + 2) * (W + 2);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -243,7 +260,11 @@ __global__ void bake_density_kernel(const float *__restrict__ src, int H, int W,
         double v = 0.0;
         if (x >= 1 && x <= W && y >= 1 && y <= H)
             for (int c = 0; c < nc; ++c) v += (double)wd[c] * (double)src[((size_t)c * H + (y - 1)) * W + (x - 1)];
-        dst[i] = (float)v;
+        if (pair) {          // the row-pair form (pack_plane_kernel)
+            dst[i * 2] = (float)v;
+            if (y >= 1) dst[(i - (W + 2)) * 2 + 1] = (float)v;
+            if (y == H + 1) dst[i * 2 + 1] = 0.0f;
+        } else dst[i] = (float)v;
     }
 }
 
@@ -900,6 +921,21 @@ extern "C" int ngf_field_create(const ngf_field_desc *d, ngf_field **out, void *
 
     NGF_CT("image upload");
     // textures: channel-last, zero-bordered
+    // The march's planes of a baked-density handle (levels 2, 3): the row-pair form (struct Tex) -- the handle is re-packed whenever the parameters change, so
+    // the cell's second row is put next to its first once, here.  Level 1 keeps the one-row gauge planes with its 16-channel density texels (its
+    // render kernel has no register to spare: bil_setup), and so do the trainer's images, which the optimiser updates in place.
+    bool pair = bake;
+#ifdef NGF_EXPERIMENTS
+    if (knob(KNOB_PAIRPACK) == 0) pair = false;          // A/B: the one-row layout, read by the kernels' RenderArgs::pairpack == 0 path
+#else
+    if (knob(KNOB_PAIRPACK) == 0) return bail(fail(NGF_E_UNSUPPORTED, "knob pairpack = 0 (the one-row layout of the march's planes) exists in libngf_hip_exp.so only"));
+#endif
+    A.pairpack = pair ? 1 : 0;
+    A.gauge_same = 0;
+    if (tri && bake) {
+        A.gauge_same = 1;
+        for (int p = 0; p < 3; ++p) A.gauge_same &= d->gauge_h[p] == d->gauge_w[0] && d->gauge_w[p] == d->gauge_w[0];
+    }
     const int app_c = bake_c ? 64 : f->app;
     for (int p = 0; p < 3; ++p) {
         const int H = d->plane_h[p], W = d->plane_w[p];
@@ -908,8 +944,8 @@ extern "C" int ngf_field_create(const ngf_field_desc *d, ngf_field **out, void *
         if (texels * (size_t)(app_c > 96 ? app_c : 96) * sizeof(float) >= ((size_t)1 << 32)) {     // the kernels address a texture with 32-bit byte offsets (tex_at)
             return bail(fail(NGF_E_UNSUPPORTED, "plane %d: %d x %d texels do not fit a 4 GiB packed texture", p, H, W));
         }
-        if ((rc = alloc_f(&f->tex[p], texels * dc, f, st)) || (rc = alloc_f(&f->tex[3 + p], texels * app_c, f, st))) return bail(rc);
-        if (bake) bake_density_kernel<<<1024, 256, 0, st>>>(d->plane[p], H, W, d->dens_dim, d->dens_w1 + p * d->dens_dim, f->tex[p]);
+        if ((rc = alloc_f(&f->tex[p], packed_plane_floats(H, W, dc, pair), f, st)) || (rc = alloc_f(&f->tex[3 + p], texels * app_c, f, st))) return bail(rc);
+        if (bake) bake_density_kernel<<<1024, 256, 0, st>>>(d->plane[p], H, W, d->dens_dim, d->dens_w1 + p * d->dens_dim, f->tex[p], pair ? 1 : 0);
         else pack_plane_kernel<<<2048, 256, 0, st>>>(d->plane[p], H, W, 0, d->dens_dim, f->tex[p]);
         if (bake_c) bake_color_kernel<<<2048, 256, 0, st>>>(d->plane[p], H, W, d->dens_dim, f->app, f->w1pd_tmp + (size_t)p * f->app, F, f->tex[3 + p]);
         else pack_plane_kernel<<<2048, 256, 0, st>>>(d->plane[p], H, W, d->dens_dim, f->app, f->tex[3 + p], tri ? 0 : 1);
@@ -917,8 +953,8 @@ extern "C" int ngf_field_create(const ngf_field_desc *d, ngf_field **out, void *
         A.app[p] = Tex{f->tex[3 + p], W, H, W + 2, (float)(W - 1), (float)(H - 1)};
         if (tri) {
             const int gh = d->gauge_h[p], gw = d->gauge_w[p];
-            if ((rc = alloc_f(&f->tex[6 + p], (size_t)(gh + 2) * (gw + 2) * 2, f, st))) return bail(rc);
-            pack_plane_kernel<<<256, 256, 0, st>>>(d->gauge[p], gh, gw, 0, 2, f->tex[6 + p]);
+            if ((rc = alloc_f(&f->tex[6 + p], packed_plane_floats(gh, gw, 2, pair), f, st))) return bail(rc);
+            pack_plane_kernel<<<256, 256, 0, st>>>(d->gauge[p], gh, gw, 0, 2, f->tex[6 + p], 0, pair ? 1 : 0);
             A.gau[p] = Tex{f->tex[6 + p], gw, gh, gw + 2, (float)(gw - 1), (float)(gh - 1)};
         }
     }
@@ -1148,6 +1184,9 @@ static int launch_render(K kernel, K kernel_split, K kernel_prod, const ngf_fiel
 template <typename P>
 static int launch_policy(const ngf_field *f, RenderArgs &A, hipStream_t st)
 {
+    if constexpr (shared_gauge<P>::value) {
+        if (!A.gauge_same) return launch_policy<GaugeAny<P>>(f, A, st);      // gauge planes of unequal sizes: every plane's cell on its own
+    }
     const size_t lds = ((size_t)((A.blob_floats + 3) & ~3) + P::WAVES * wave_lds_floats<P>()) * sizeof(float);
     if (lds > 160 * 1024) return fail(NGF_E_ARG, "this waves-per-CU setting needs %zu bytes of LDS (> 160 KiB)", lds);
     constexpr int wide = P::INFOINV ? 16 : 8;          // measured best full-frame tile width (profiles/r01_split_march.txt; InfoInv: 30.3 vs 29.3 Mray/s)
@@ -1162,6 +1201,9 @@ static int launch_policy(const ngf_field *f, RenderArgs &A, hipStream_t st)
 template <typename P, int NM, int NS, int TW>
 static int launch_pc(const ngf_field *f, RenderArgs &A, hipStream_t st)
 {
+    if constexpr (shared_gauge<P>::value) {
+        if (!A.gauge_same) return launch_pc<GaugeAny<P>, NM, NS, TW>(f, A, st);
+    }
     const size_t lds = ((size_t)((A.blob_floats + 3) & ~3) + PcLds<NM>::TOTAL) * sizeof(float);
     if (lds > 160 * 1024) return fail(NGF_E_ARG, "the specialised kernel needs %zu bytes of LDS (> 160 KiB)", lds);
     const unsigned slot = f->next_counter.fetch_add(1) % kCounters;
@@ -1378,7 +1420,8 @@ static int launch_alpha(const ngf_field *f, const float *xyz, const Lattice &L, 
             hipLaunchKernelGGL(alpha_kernel<InfoInvPolicy>, dim3((unsigned)grid), dim3(256), lds, st, A, xyz, L, n, length, alpha);
         }
     } else if (f->flags & NGF_F_BAKE_DENSITY) {
-        hipLaunchKernelGGL((alpha_kernel<TriPlanePolicy<true, false, 8, 1>>), dim3((unsigned)grid), dim3(256), 0, st, A, xyz, L, n, length, alpha);
+        if (A.gauge_same) hipLaunchKernelGGL((alpha_kernel<TriPlanePolicy<true, false, 8, 1>>), dim3((unsigned)grid), dim3(256), 0, st, A, xyz, L, n, length, alpha);
+        else hipLaunchKernelGGL((alpha_kernel<GaugeAny<TriPlanePolicy<true, false, 8, 1>>>), dim3((unsigned)grid), dim3(256), 0, st, A, xyz, L, n, length, alpha);
     } else {
         hipLaunchKernelGGL((alpha_kernel<TriPlanePolicy<false, false, 8, 1>>), dim3((unsigned)grid), dim3(256), 0, st, A, xyz, L, n, length, alpha);
     }

@@ -122,16 +122,22 @@ __device__ __forceinline__ void pe_ladder(float x, float sn[F], float cs[F])
 // ---- TriPlane density at the gauge-shifted coordinates ------------------------------------------
 // cells: if not null, the three bilinear cells of the fetch (the colour fetch of an active sample uses the same ones: same coordinates, plane of the
 // same size -- they travel in the 12-float queue record, REC12)
-template <bool BAKED>
+// PAIR (baked planes only): the plane is in the row-pair form (struct Tex) -- the cell's four taps {t(x0,y0), t(x0,y0+1), t(x0+1,y0), t(x0+1,y0+1)} are
+// one 16-byte load, one cache line seven times out of eight, instead of two 8-byte loads a padded row apart.  Same values into the same bil_mix.
+template <bool BAKED, bool PAIR = false>
 __device__ __forceinline__ float triplane_density_feature(const RenderArgs &A, const float t[6], Bil *cells = nullptr)
 {
+    static_assert(BAKED || !PAIR, "only the 1-channel baked density planes have a row-pair form");
     float f = 0.0f;
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
         const Tex tx = karg_tex(offsetof(RenderArgs, dens) + p * sizeof(Tex));
         Bil b = bil_setup<BAKED>(t[2 * p], t[2 * p + 1], tx);
         if (cells) cells[p] = b;
-        if (BAKED) {
+        if (BAKED && PAIR) {
+            const f32x4_a8 q = *tex_at<f32x4_a8>(tx.p, (uint32_t)b.idx * 2u);
+            f += bil_mix(b, q[0], q[2], q[1], q[3]);
+        } else if (BAKED) {
             const float *q = tex_at<float>(tx.p, (uint32_t)b.idx), *q1 = tex_at<float>(tx.p, (uint32_t)(b.idx + tx.stride));
             f += bil_mix(b, q[0], q[1], q1[0], q1[1]);
         } else {
@@ -163,20 +169,48 @@ __device__ __forceinline__ float triplane_density_feature(const RenderArgs &A, c
 }
 
 // compute_gauge (Field.py:53-75): three 2-channel bilinear fetches + the reference's add order
-template <bool MED3 = true>
+// PAIR: the gauge planes are in the row-pair form (struct Tex): texel x0 holds {g(x0,y0), g(x0,y0+1)}, texel x0 + 1 the other two taps -- two 16-byte loads
+// 16 bytes apart instead of two 16-byte row halves a padded row apart.
+// SAME (PAIR only; the host checks it: RenderArgs::gauge_same): the three planes are square and of one size, so a cell's x part -- scale, floor, fraction,
+// clamp, in-range compare -- depends on the coordinate alone: three axis set-ups (x, y, z) instead of six, the same operations on the same inputs, hence the
+// same bits.  A compile-time choice (GaugeAny below): as a wave-uniform branch on the flag it cost the level-2 / 3 kernels 36 B of scratch per lane.
+template <bool MED3 = true, bool PAIR = false, bool SAME = false>
 __device__ __forceinline__ void triplane_gauge(const RenderArgs &A, const float x[3], int gauge_on, float t[6])
 {
     const float u[3] = {x[0], x[1], x[0]}, v[3] = {x[1], x[2], x[2]};   // xy, yz, xz
     if (gauge_on) {
         float d[3][2];
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const Tex tx = karg_tex(offsetof(RenderArgs, gau) + p * sizeof(Tex));
-            Bil b = bil_setup<MED3>(u[p], v[p], tx);
-            const f32x2 *g = tex_at<f32x2>(tx.p, (uint32_t)b.idx * 2u), *g1 = tex_at<f32x2>(tx.p, (uint32_t)(b.idx + tx.stride) * 2u);
-            f32x2 g00 = g[0], g10 = g[1], g01 = g1[0], g11 = g1[1];
+        auto fetch = [&](int p, const Tex &tx, const Bil &b) {
+            f32x2 g00, g10, g01, g11;
+            if constexpr (PAIR) {
+                const f32x4 *g = tex_at<f32x4>(tx.p, (uint32_t)b.idx * 4u);
+                const f32x4 a = g[0], c = g[1];
+                g00 = f32x2{a[0], a[1]}; g01 = f32x2{a[2], a[3]}; g10 = f32x2{c[0], c[1]}; g11 = f32x2{c[2], c[3]};
+            } else {
+                const f32x2 *g = tex_at<f32x2>(tx.p, (uint32_t)b.idx * 2u), *g1 = tex_at<f32x2>(tx.p, (uint32_t)(b.idx + tx.stride) * 2u);
+                g00 = g[0]; g10 = g[1]; g01 = g1[0]; g11 = g1[1];
+            }
             d[p][0] = bil_mix(b, g00[0], g10[0], g01[0], g11[0]);
             d[p][1] = bil_mix(b, g00[1], g10[1], g01[1], g11[1]);
+        };
+        if constexpr (PAIR && MED3 && SAME) {
+            const Tex t0 = karg_tex(offsetof(RenderArgs, gau));
+            BilAxis ax[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ax[k] = bil_axis(x[k], t0.fw);
+            const int ua[3] = {0, 1, 0}, va[3] = {1, 2, 2};
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                Tex tx = t0;
+                tx.p = karg<const float *>(offsetof(RenderArgs, gau) + p * sizeof(Tex) + offsetof(Tex, p));
+                fetch(p, tx, bil_from_axes(ax[ua[p]], ax[va[p]], t0.stride));
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                const Tex tx = karg_tex(offsetof(RenderArgs, gau) + p * sizeof(Tex));
+                fetch(p, tx, bil_setup<MED3>(u[p], v[p], tx));
+            }
         }
         // d[0] = dxy, d[1] = dyz, d[2] = dxz
         t[0] = (u[0] + d[0][0]) + d[2][0];  t[1] = (v[0] + d[0][1]) + d[1][0];
@@ -213,17 +247,35 @@ struct TriPlanePolicy {
     // plane on the cell -- all 64 lanes of a pass used to redo the three setups of their 16 samples that the march had already done.
     static constexpr bool REC12 = WAVES_ == 12 && NSTEP_ == 1 && !PROFILE_;
     static constexpr bool GATHER_QUAD = BAKE_C;                 // the shade's gather lane 4 s + kq works for sample lane >> 2 (ngf_shade16.hpp mlp_pass16_baked): shade12 takes ITS cells
-    __device__ static __forceinline__ float sigma(const RenderArgs &A, const float *, bool valid, const float x[3], int, float t[6], Bil *cells = nullptr)
+    static constexpr bool SHARED_GAUGE = BAKE_D;                 // sigma() takes the shared-axis gauge set-up: launched only for RenderArgs::gauge_same, GaugeAny<P> otherwise
+    template <bool SAME>
+    __device__ static __forceinline__ float sigma_impl(const RenderArgs &A, bool valid, const float x[3], float t[6], Bil *cells)
     {
         // branch-free: out-of-box samples have out-of-range coordinates, for which bil_setup clamps the
         // texel index and zeroes the weights, so their gathers are safe and their result is discarded.
         // Without the branch the NSTEP independent steps share one basic block and their gathers overlap.
         float tt[6];
-        triplane_gauge<BAKE_D>(A, x, A.mode, tt);
-        const float sg = softplus_shift(triplane_density_feature<BAKE_D>(A, tt, cells));
+        float f;
+        // levels 2 and 3 read their march planes in the row-pair form (struct Tex).  The experiment library keeps the one-row readers behind
+        // RenderArgs::pairpack (a handle created under ngf_debug_set("pairpack", 0)): one build measures both and the tests compare their bits.
+#ifdef NGF_EXPERIMENTS
+        if (BAKE_D && !A.pairpack) {
+            triplane_gauge<BAKE_D, false>(A, x, A.mode, tt);
+            f = triplane_density_feature<BAKE_D, false>(A, tt, cells);
+        } else
+#endif
+        {
+            triplane_gauge<BAKE_D, BAKE_D, SAME>(A, x, A.mode, tt);
+            f = triplane_density_feature<BAKE_D, BAKE_D>(A, tt, cells);
+        }
+        const float sg = softplus_shift(f);
 #pragma unroll
         for (int k = 0; k < 6; ++k) t[k] = valid ? tt[k] : 0.0f;
         return valid ? sg : 0.0f;
+    }
+    __device__ static __forceinline__ float sigma(const RenderArgs &A, const float *, bool valid, const float x[3], int, float t[6], Bil *cells = nullptr)
+    {
+        return sigma_impl<true>(A, valid, x, t, cells);
     }
     // vf: the owner ray's 16 cached view inputs (VLDS) or nullptr; od: the owner ray's direction
     static constexpr bool VIEW_FOLD = VLDS;                      // small split tiles: b1 + W1[:, view].view once per ray per tile
@@ -269,6 +321,19 @@ struct MaskSkip : P {
     static constexpr bool MASK_SKIP = true;
 #endif
 };
+
+// The same kernel for a field whose gauge planes are NOT three squares of one size (RenderArgs::gauge_same = 0; the reference's are 256 x 256 each): every
+// plane's cell set up on its own, as before.  launch_policy / launch_alpha pick it; the names of the default instantiations stay what they were.
+template <typename P>
+struct GaugeAny : P {
+    static constexpr bool SHARED_GAUGE = false;
+    __device__ static __forceinline__ float sigma(const RenderArgs &A, const float *, bool valid, const float x[3], int, float t[6], Bil *cells = nullptr)
+    {
+        return P::template sigma_impl<false>(A, valid, x, t, cells);
+    }
+};
+template <typename P, typename = void> struct shared_gauge : std::false_type {};
+template <typename P> struct shared_gauge<P, std::void_t<decltype(P::SHARED_GAUGE)>> : std::integral_constant<bool, P::SHARED_GAUGE> {};
 
 // NGF_F_SPLIT_BF16: the colour MLP on the bf16 matrix pipe with 3-term split operands (ngf_shade_bf16.hpp).  Split tiles of <= 8 rays
 // only (the wave keeps the view inputs of 8 rays); 8 waves per CU (the pass needs ~200 registers).
