@@ -1,20 +1,22 @@
 // ngf_field.hip -- C ABI (include/ngf.h), TriPlane / InfoInv part: field handle, render / march / decode / alpha-mask / ray
-// entry points and the training step (they share the plane packing kernels).  No torch, no CPU fallback: every entry point
-// runs HIP kernels or fails.  Build: see Makefile (hipcc --offload-arch=gfx950 -O3 -ffp-contract=off).
+// entry points, and the services of ngf_host.hpp (error slot, knobs, LDS poisoning).  The TriPlane training step is ngf_train.hip (it shares
+// the plane packing kernels of ngf_pack.hpp).  No torch, no CPU fallback: every entry point runs HIP kernels or fails.  Build: see Makefile
+// (hipcc --offload-arch=gfx950 -O3 -ffp-contract=off).
 #include <map>
 #include <mutex>
 #include <utility>
 
 #include "ngf_host.hpp"
 #include "ngf_infoinv.hpp"
+#include "ngf_pack.hpp"
 #include "ngf_render.hpp"
+#include "ngf_alpha.hpp"
 #ifdef NGF_EXPERIMENTS      // libngf_hip_exp.so only (make: second target): kernels that were built, measured and lost -- specialised march / shade
                             // waves, LDS-staged texture strips -- and the tuning variants (8 / 16 waves, two steps per lane, section profile).  The
                             // product library carries only kernels that can be the default; the experiment tests load the other one.
 #include "ngf_render_pc.hpp"
 #include "ngf_stage.hpp"
 #endif
-#include "ngf_train.hpp"
 
 using namespace ngf;
 
@@ -164,53 +166,12 @@ static inline void field_use(const ngf_field *f, hipStream_t st)
     f->last_stream.store((void *)st, std::memory_order_relaxed);
 }
 
-// ---- packing kernels -----------------------------------------------------------------------------
-// NCHW [C,H,W] channels [c0,c0+nc) -> zero-bordered channel-last [(H+2)][(W+2)][nc]
-// perm = 1: the colour channels in the order of infoinv_split_channel (InfoInv NGF_F_SPLIT_BF16, nc = 72)
-// pair = 1: the row-pair form (struct Tex, ngf_device.hpp) [(H+2)][(W+2)][2][nc]: slot 0 of padded texel (x, y) holds (x, y), slot 1 holds (x, y + 1) --
-// every value is stored twice, as its own texel's slot 0 and as slot 1 of the texel above; the last padded row pairs with zeros.
-__global__ void pack_plane_kernel(const float *__restrict__ src, int H, int W, int c0, int nc, float *__restrict__ dst, int perm = 0, int pair = 0)
-{
-    const size_t total = (size_t)(H + 2) * (W + 2) * nc;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % nc);
-        const size_t tx = i / nc;
-        const int x = (int)(tx % (W + 2)), y = (int)(tx / (W + 2));
-        float v = 0.0f;
-        if (x >= 1 && x <= W && y >= 1 && y <= H) v = src[((size_t)(c0 + (perm ? infoinv_split_channel(c) : c)) * H + (y - 1)) * W + (x - 1)];
-        if (pair) {
-            dst[tx * 2 * nc + c] = v;
-            if (y >= 1) dst[((tx - (W + 2)) * 2 + 1) * nc + c] = v;
-            if (y == H + 1) dst[(tx * 2 + 1) * nc + c] = 0.0f;
-        } else dst[i] = v;
-    }
-}
-
-// Rows of a packed plane of H rows as allocated: the padded rows 0 .. H + 1, in both forms (the row-pair form doubles the texel, not the rows).  The march's
-// cells start at padded (cx, cy) in [0, W] x [0, H] (bil_setup) and read texels idx, idx + 1 of row cy -- and, in the one-row form, of row cy + 1.
-static inline size_t packed_plane_floats(int H, int W, int nc, bool pair) { return (size_t)(H + 2) * (W + 2) * nc * (pair ? 2 : 1); }
-
-// tests: the size arithmetic above
+// ---- packing kernels: pack_plane_kernel, packed_plane_floats, mask_cells_kernel are in ngf_pack.hpp (the TriPlane trainer packs with them too) ----
+// tests: the size arithmetic of packed_plane_floats
 extern "C" int64_t ngf_debug_packed_plane_floats(int32_t H, int32_t W, int32_t nc, int32_t pair)
 {
     if (H < 1 || W < 1 || nc < 1) return -1;
     return (int64_t)packed_plane_floats(H, W, nc, pair != 0);
-}
-
-// Alpha mask, second image (round 6): per trilinear cell -- base corner (z, y, x) in -1 .. D-1 / H-1 / W-1 -- one byte with the bits of its 8 corners
-// (bit dz*4 + dy*2 + dx; corners outside the volume are 0 = grid_sample's zeros padding), so that mask_occupied needs ONE gather per sample.
-__global__ void __launch_bounds__(256) mask_cells_kernel(const uint8_t *__restrict__ bits, int D, int H, int W, uint8_t *__restrict__ cells)
-{
-    ngf::MaskVol m{};
-    m.bits = bits; m.D = D; m.H = H; m.W = W;
-    const size_t total = (size_t)(D + 1) * (H + 1) * (W + 1);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % (size_t)(W + 1)) - 1, y = (int)((i / (size_t)(W + 1)) % (size_t)(H + 1)) - 1, z = (int)(i / ((size_t)(W + 1) * (H + 1))) - 1;
-        unsigned c = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c |= (unsigned)ngf::mask_bit(m, z + (k >> 2), y + ((k >> 1) & 1), x + (k & 1)) << k;
-        cells[i] = (uint8_t)c;
-    }
 }
 
 // Alpha mask, block images (round 6): empty-space skipping.  Blocks of B^3 cells, B = 2^LOG, over the cell indices -16 .. size + 16 per axis (block = (cell index + 16) >> LOG).
@@ -1507,782 +1468,3 @@ extern "C" int ngf_generate_rays_dtu(int32_t H, int32_t W, const float *focal, c
     HIP_TRY(hipGetLastError());
     return NGF_OK;
 }
-
-// ================================ training step ============================================================
-enum { TP_PLANE = 0, TP_GAUGE = 3, TP_DENS_W = 6, TP_DENS_B = 7, TP_BASIS = 8, TP_W1 = 9, TP_B1 = 10, TP_W2 = 11, TP_B2 = 12, TP_W3 = 13,
-       TP_B3 = 14, TP_COUNT = 15 };
-
-struct ngf_trainer {
-    int dev = 0;                             // the device the trainer's buffers and streams live on
-    ngf_train_desc d;
-    TrainArgs proto;
-    std::vector<void *> allocs;
-    float *tex_d[3] = {}, *tex_a[3] = {}, *tex_g[3] = {};
-    float *g_d[3] = {}, *g_a[3] = {}, *g_g[3] = {};
-    float *g_gb[3] = {};                     // gauge-plane gradients in the blocked layout the scatter writes (g_g: [texel][2])
-    float *q_d[3] = {}, *d_d[3] = {};        // wd-projected density planes, scalar density-gradient images
-    float *fwd_image = nullptr, *bwd_image = nullptr;      // LDS images of the colour MLP (train_fold_kernel)
-    float *fwd16_image = nullptr;                          // ... and the forward's image in the eval pass's layout (train_color_fwd16_kernel)
-    float *g_dense[TP_COUNT] = {};          // reference-layout gradient buffers of the MLP parameters (index TP_*)
-    int64_t dense_n[TP_COUNT] = {};
-    uint8_t *mask = nullptr;
-    uint8_t *mask_cells = nullptr;
-    bool tex_fresh[6] = {};                 // the packed copy of plane / gauge plane k holds the parameter's current values
-    char *zero_arena = nullptr;             // every buffer a step accumulates into (gradients, M, loss): one memset per step
-    size_t zero_bytes = 0;
-    int64_t chunk = 0;
-    bool speculative = false;               // chunk_samples < 0: `chunk` rows, never a host round trip; a batch with more active samples is flagged on the device
-    int32_t *overflow = nullptr;            // device: [0] this step's batch had more active samples than rows (Adam then skips), [1] how often that happened
-    int64_t bytes = 0;
-    int num_cus = 256;
-    // after the colour backward the step forks: weight-gradient GEMMs | colour-plane scatter | density / gauge backward are independent
-    // chains of kernels none of which fills the device on its own (row transposes, LDS latency, the atomic unit); ngf_train_adam_all
-    // updates the three planes side by side
-    static constexpr int kAux = 2;
-    hipStream_t aux[kAux] = {nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[kAux] = {nullptr, nullptr};
-    bool has_adam = true;                   // false: built without Adam moments (ngf_train_forward / ngf_train_backward_grad only; ngf_train_adam* refuse)
-    // what ngf_train_forward leaves for ngf_train_backward_grad (the two-call form of the step)
-    struct Pending {
-        bool valid = false;
-        TrainArgs T;
-        bool fork = false, no_sync = false, single = true;
-        int64_t n = 0, list_len = 0;
-        int32_t n_samples = 0;
-        int64_t ticket = 0;
-    } pending;
-    int64_t tickets = 0;
-};
-
-template <typename T>
-static int tr_alloc(ngf_trainer *t, T **p, size_t count)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, count * sizeof(T) + 64) != hipSuccess) return fail(NGF_E_HIP, "hipMalloc(%zu bytes) failed for the trainer", count * sizeof(T));
-    t->allocs.push_back(q);
-    t->bytes += (int64_t)(count * sizeof(T));
-    *p = (T *)q;
-    return NGF_OK;
-}
-
-extern "C" int ngf_trainer_destroy(ngf_trainer *t)
-{
-    if (!t) return NGF_OK;
-    DeviceScope ds(t->dev);              // hipFree / stream teardown on the trainer's device, whatever is current in the calling thread
-    for (void *q : t->allocs) (void)hipFree(q);
-    for (int k = 0; k < ngf_trainer::kAux; ++k) {
-        if (t->aux[k]) { (void)hipStreamSynchronize(t->aux[k]); (void)hipStreamDestroy(t->aux[k]); }
-        if (t->ev_join[k]) (void)hipEventDestroy(t->ev_join[k]);
-    }
-    if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
-    delete t;
-    return NGF_OK;
-}
-
-extern "C" int64_t ngf_trainer_bytes(const ngf_trainer *t) { return t ? t->bytes : 0; }
-extern "C" int32_t ngf_sizeof_train_desc(void) { return (int32_t)sizeof(ngf_train_desc); }
-
-extern "C" int ngf_trainer_create(const ngf_train_desc *d, ngf_trainer **out, void *hip_stream)
-{
-    if (!d || !out) return fail(NGF_E_ARG, "ngf_trainer_create: null argument");
-    if (d->max_rays <= 0 || d->max_samples <= 0) return fail(NGF_E_ARG, "ngf_trainer_create: max_rays / max_samples must be positive");
-    for (int p = 0; p < 3; ++p) {
-        if (!d->plane[p] || d->plane_h[p] < 2 || d->plane_w[p] < 2) return fail(NGF_E_ARG, "plane %d missing or smaller than 2x2", p);
-        if (!d->gauge[p] || d->gauge_h[p] < 2 || d->gauge_w[p] < 2) return fail(NGF_E_ARG, "gauge plane %d missing or smaller than 2x2", p);
-    }
-    if (!d->dens_w || !d->dens_b || !d->basis || !d->w1 || !d->b1 || !d->w2 || !d->b2 || !d->w3 || !d->b3)
-        return fail(NGF_E_ARG, "ngf_trainer_create: missing MLP parameter");
-    // Adam moments: all fifteen pairs, or none at all (a trainer that only serves ngf_train_forward / ngf_train_backward_grad -- the caller's
-    // own optimiser applies the gradients, e.g. torch.optim.Adam in the reference's loop, TriPlane/main.py:241,294-296)
-    int moments = 0;
-    for (int k = 0; k < TP_COUNT; ++k) moments += (d->exp_avg[k] ? 1 : 0) + (d->exp_avg_sq[k] ? 1 : 0);
-    if (moments != 0 && moments != 2 * TP_COUNT) return fail(NGF_E_ARG, "ngf_trainer_create: Adam state must be given for all %d parameters or for none", (int)TP_COUNT);
-    ngf_trainer *t = new (std::nothrow) ngf_trainer();
-    if (!t) return fail(NGF_E_HIP, "out of host memory");
-    t->d = *d;
-    t->has_adam = moments != 0;
-    auto bail = [&](int rc) { ngf_trainer_destroy(t); return rc; };
-    hipStream_t st = (hipStream_t)hip_stream;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) t->num_cus = prop.multiProcessorCount;
-    t->dev = dev;
-    int rc;
-    for (int k = 0; k < ngf_trainer::kAux; ++k)
-        if (hipStreamCreateWithFlags(&t->aux[k], hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&t->ev_join[k], hipEventDisableTiming) != hipSuccess)
-            return bail(fail(NGF_E_HIP, "trainer: stream / event creation failed"));
-    if (hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming) != hipSuccess) return bail(fail(NGF_E_HIP, "trainer: event creation failed"));
-    TrainArgs &T = t->proto;
-    memset(&T, 0, sizeof(T));
-    RenderArgs &A = T.R;
-    const int64_t dn[TP_COUNT] = {0, 0, 0, 0, 0, 0, 48, 1, 144 * 144, 64 * 159, 64, 64 * 64, 64, 3 * 64, 3};
-    // blocked gradient images (ngf_train.hpp, scatter_blocked): 16-float blocks of 4x4 texels (D_p) / 4x2 texels x 2 channels (gauge)
-    auto dblk = [&](int p) { return (size_t)((d->plane_w[p] + 2 + 3) / 4) * ((d->plane_h[p] + 2 + 3) / 4) * 16; };
-    auto gblk = [&](int p) { return (size_t)((d->gauge_w[p] + 2 + 3) / 4) * ((d->gauge_h[p] + 2 + 1) / 2) * 16; };
-    // bins of the colour-plane scatter (ngf_train.hpp section 5b): 8x8 blocks of cells of the padded planes
-    int nbins = 0;
-    for (int p = 0; p < 3; ++p) {
-        T.bin_base[p] = nbins;
-        T.bin_nbx[p] = (d->plane_w[p] + 2 + 7) / 8;
-        nbins += T.bin_nbx[p] * ((d->plane_h[p] + 2 + 7) / 8);
-    }
-    T.nbins = nbins;
-    {   // the zero arena: [per plane: D_p, gauge gradient] [MLP gradients] [M] [loss] [bin counters], 256-byte aligned pieces
-        size_t total = 0;
-        auto add = [&](size_t floats) { total += (floats * sizeof(float) + 255) & ~(size_t)255; };
-        for (int p = 0; p < 3; ++p) { add(dblk(p)); add(gblk(p)); }
-        for (int k = TP_DENS_W; k < TP_COUNT; ++k) add((size_t)dn[k]);
-        add((size_t)64 * 144); add(4);
-        add((size_t)nbins + 1);
-        if ((rc = tr_alloc(t, &t->zero_arena, total))) return bail(rc);
-        t->zero_bytes = total;
-    }
-    size_t carved = 0;
-    auto carve = [&](size_t floats) {
-        float *q = reinterpret_cast<float *>(t->zero_arena + carved);
-        carved += (floats * sizeof(float) + 255) & ~(size_t)255;
-        return q;
-    };
-    for (int p = 0; p < 3; ++p) {
-        const int H = d->plane_h[p], W = d->plane_w[p], gh = d->gauge_h[p], gw = d->gauge_w[p];
-        const size_t tex = (size_t)(H + 2) * (W + 2), gtex = (size_t)(gh + 2) * (gw + 2);
-        if ((rc = tr_alloc(t, &t->tex_d[p], tex * 16)) || (rc = tr_alloc(t, &t->tex_a[p], tex * 48)) || (rc = tr_alloc(t, &t->tex_g[p], gtex * 2)) ||
-            (rc = tr_alloc(t, &t->q_d[p], tex)) || (rc = tr_alloc(t, &t->g_d[p], tex * 16)) || (rc = tr_alloc(t, &t->g_g[p], gtex * 2)))
-            return bail(rc);
-        t->d_d[p] = carve(dblk(p)); t->g_gb[p] = carve(gblk(p));
-        // the colour planes' gradients are WRITTEN by train_bin_gather_kernel (every texel): no fill per step
-        if ((rc = tr_alloc(t, &t->g_a[p], tex * 48))) return bail(rc);
-        if (hipMemsetAsync(t->g_a[p], 0, tex * 48 * sizeof(float), st) != hipSuccess) return bail(fail(NGF_E_HIP, "trainer setup failed"));
-        T.d_bw[p] = (W + 2 + 3) / 4; T.g_bw[p] = (gw + 2 + 3) / 4;
-        A.dens[p] = Tex{t->tex_d[p], W, H, W + 2, (float)(W - 1), (float)(H - 1)};
-        A.app[p] = Tex{t->tex_a[p], W, H, W + 2, (float)(W - 1), (float)(H - 1)};
-        A.gau[p] = Tex{t->tex_g[p], gw, gh, gw + 2, (float)(gw - 1), (float)(gh - 1)};
-        T.g_dens[p] = t->g_d[p]; T.g_app[p] = t->g_a[p]; T.g_gau[p] = t->g_gb[p];
-        T.q_dens[p] = t->q_d[p]; T.d_dens[p] = t->d_d[p];
-    }
-    for (int k = TP_DENS_W; k < TP_COUNT; ++k) {
-        t->dense_n[k] = dn[k];
-        t->g_dense[k] = carve((size_t)dn[k]);
-    }
-    T.M = carve((size_t)64 * 144);
-    T.loss = reinterpret_cast<double *>(carve(4));
-    T.bin_count = reinterpret_cast<int32_t *>(carve((size_t)nbins + 1));
-    if (carved != t->zero_bytes) return bail(fail(NGF_E_ARG, "trainer: zero arena layout mismatch"));
-    T.wd = d->dens_w; T.bd = d->dens_b; T.basis = d->basis; T.w1 = d->w1; T.b1 = d->b1; T.w2 = d->w2; T.b2 = d->b2; T.w3 = d->w3; T.b3 = d->b3;
-    T.g_wd = t->g_dense[TP_DENS_W]; T.g_bd = t->g_dense[TP_DENS_B];
-    if ((rc = tr_alloc(t, &T.prof, (size_t)16))) return bail(rc);
-    if (hipMemsetAsync(T.prof, 0, 16 * sizeof(unsigned long long), st) != hipSuccess) return bail(fail(NGF_E_HIP, "trainer setup failed"));
-    T.g_b1 = t->g_dense[TP_B1]; T.g_b2 = t->g_dense[TP_B2]; T.g_b3 = t->g_dense[TP_B3];
-    for (int k = 0; k < 3; ++k) {
-        A.a0[k] = d->aabb[k];
-        A.a1[k] = d->aabb[3 + k];
-        A.inv[k] = 2.0f / (d->aabb[3 + k] - d->aabb[k]);
-    }
-    A.near_ = d->near_; A.far_ = d->far_; A.step = d->step; A.dscale = d->distance_scale; A.thr = d->weight_thres;
-    if (d->mask_bits) {
-        const size_t nbytes = ((size_t)d->mask_d * d->mask_h * d->mask_w + 7) / 8;
-        if ((rc = tr_alloc(t, &t->mask, nbytes))) return bail(rc);
-        if (hipMemcpyAsync(t->mask, d->mask_bits, nbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return bail(fail(NGF_E_HIP, "copying the alpha mask failed"));
-        A.mask.bits = t->mask;
-        A.mask.D = d->mask_d; A.mask.H = d->mask_h; A.mask.W = d->mask_w;
-        const size_t ncells = (size_t)(d->mask_d + 1) * (d->mask_h + 1) * (d->mask_w + 1);
-        if (ncells >= ((size_t)1 << 32)) return bail(fail(NGF_E_ARG, "alpha mask of %d x %d x %d cells: the cell image is indexed with 32 bits", d->mask_d, d->mask_h, d->mask_w));
-        if ((rc = tr_alloc(t, &t->mask_cells, ncells))) return bail(rc);
-        hipLaunchKernelGGL(mask_cells_kernel, dim3(2048), dim3(256), 0, st, (const uint8_t *)t->mask, d->mask_d, d->mask_h, d->mask_w, t->mask_cells);
-        if (hipGetLastError() != hipSuccess) return bail(fail(NGF_E_HIP, "mask_cells_kernel failed to launch"));
-        A.mask.cells = t->mask_cells;
-        for (int k = 0; k < 3; ++k) {
-            A.mask.a0[k] = d->mask_aabb[k];
-            A.mask.inv[k] = 1.0f / (d->mask_aabb[3 + k] - d->mask_aabb[k]) * 2;
-        }
-    }
-    const size_t cap = (size_t)d->max_rays * d->max_samples;
-    // activation rows kept at once: by default the whole batch (1.7 KB per sample -- 6.2 GB for 4096 rays x 884 samples; the MI355X
-    // has 288 GB), which also lets the step run without a host round trip; at most ~16 GB unless the caller asks otherwise
-    // chunk_samples < 0 (speculative rows): |chunk_samples| rows, the step never waits for the host; a batch with more active samples than that
-    // is flagged by the device (Adam skips the step, ngf_train_overflow_count reports it) -- 4096 x 884 pairs with rows for a third of them
-    // are 3.4 GiB instead of 9.0
-    t->speculative = d->chunk_samples < 0;
-    const int64_t want = d->chunk_samples < 0 ? -d->chunk_samples : d->chunk_samples;
-    t->chunk = want > 0 ? want : (int64_t)std::min<size_t>(cap, (size_t)9 << 20);
-    if ((size_t)t->chunk > cap) t->chunk = (int64_t)((cap + 15) & ~(size_t)15);
-    if (want <= 0 && (size_t)t->chunk >= cap) t->chunk = (int64_t)((cap + 15) & ~(size_t)15);
-    if (t->speculative) t->chunk = (t->chunk + 15) & ~(int64_t)15;
-    if ((rc = tr_alloc(t, &t->overflow, 2))) return bail(rc);
-    if (hipMemsetAsync(t->overflow, 0, 2 * sizeof(int32_t), st) != hipSuccess) return bail(fail(NGF_E_HIP, "trainer setup failed"));
-    if ((rc = tr_alloc(t, &T.et, cap)) || (rc = tr_alloc(t, &T.sg, cap)) || (rc = tr_alloc(t, &T.w, cap)) || (rc = tr_alloc(t, &T.dx, cap)) || (rc = tr_alloc(t, &T.c, cap * 3)) ||
-        (rc = tr_alloc(t, &T.dt, cap * 6)) || (rc = tr_alloc(t, &T.G, (size_t)d->max_rays * 3)) || (rc = tr_alloc(t, &T.count, (size_t)d->max_rays)) ||
-        (rc = tr_alloc(t, &T.offset, (size_t)d->max_rays + 1)) || (rc = tr_alloc(t, &T.list, cap * 2)) || (rc = tr_alloc(t, &T.list_w, cap)) ||
-        (rc = tr_alloc(t, &t->fwd_image, (size_t)kFwdImage)) || (rc = tr_alloc(t, &t->bwd_image, (size_t)kBwdImage)) || (rc = tr_alloc(t, &t->fwd16_image, (size_t)MlpLayout16<48>::TOTAL)) ||
-        (rc = tr_alloc(t, &T.bin_off, (size_t)nbins + 1)) || (rc = tr_alloc(t, &T.bin_unit, (size_t)nbins + 1)) || (rc = tr_alloc(t, &T.unit_total, (size_t)1)))
-        return bail(rc);
-    // The activation rows (576 floats per sample + the 18 of its scatter pairs).  If the whole-batch default does not fit the free HBM, fall back to round 1's chunked
-    // mode (262 144 rows = 453 MB; the colour kernels then run chunk by chunk and the step reads the active count on the host) instead of
-    // failing the create -- an explicit chunk_samples is taken as asked.
-    for (int attempt = 0;; ++attempt) {
-        const size_t ch = (size_t)t->chunk, mark = t->allocs.size();
-        const int64_t bytes_mark = t->bytes;
-        T.bin_cap = (int32_t)ch;
-        if (!((rc = tr_alloc(t, &T.F, ch * 144)) || (rc = tr_alloc(t, &T.V, ch * 16)) || (rc = tr_alloc(t, &T.H1, ch * 64)) || (rc = tr_alloc(t, &T.H2, ch * 64)) ||
-              (rc = tr_alloc(t, &T.D3, ch * 16)) || (rc = tr_alloc(t, &T.D2, ch * 64)) || (rc = tr_alloc(t, &T.D1, ch * 64)) ||
-              (rc = tr_alloc(t, &T.DF, ch * 144)) || (rc = tr_alloc(t, &T.pair_cell, ch * 3)) || (rc = tr_alloc(t, &T.pair_rank, ch * 3)) ||
-              (rc = tr_alloc(t, &T.pair_w, ch * 12)) || (rc = tr_alloc(t, &T.perm, ch * 3)) ||
-              (rc = tr_alloc(t, &T.units, ((size_t)nbins + ch * 3 / kBinChunk + 8) * 3)) ||
-              (rc = tr_alloc(t, &T.slab, ((size_t)nbins + ch * 3 / kBinChunk + 8) * kBinTile))))
-            break;
-        while (t->allocs.size() > mark) { (void)hipFree(t->allocs.back()); t->allocs.pop_back(); }
-        t->bytes = bytes_mark;
-        (void)hipGetLastError();
-        if (attempt > 0 || d->chunk_samples != 0 || ch <= ((size_t)1 << 18)) return bail(rc);
-        t->chunk = (int64_t)1 << 18;
-    }
-    // the packed copies (their zero borders are written here and never again) and defined gradients before the first backward
-    for (int p = 0; p < 3; ++p) {
-        pack_plane_kernel<<<2048, 256, 0, st>>>(d->plane[p], d->plane_h[p], d->plane_w[p], 0, 16, t->tex_d[p]);
-        pack_plane_kernel<<<2048, 256, 0, st>>>(d->plane[p], d->plane_h[p], d->plane_w[p], 16, 48, t->tex_a[p]);
-        pack_plane_kernel<<<256, 256, 0, st>>>(d->gauge[p], d->gauge_h[p], d->gauge_w[p], 0, 2, t->tex_g[p]);
-        t->tex_fresh[p] = t->tex_fresh[3 + p] = true;
-        if (hipMemsetAsync(t->g_d[p], 0, (size_t)(d->plane_h[p] + 2) * (d->plane_w[p] + 2) * 16 * sizeof(float), st) != hipSuccess ||
-            hipMemsetAsync(t->g_g[p], 0, (size_t)(d->gauge_h[p] + 2) * (d->gauge_w[p] + 2) * 2 * sizeof(float), st) != hipSuccess)
-            return bail(fail(NGF_E_HIP, "trainer setup failed"));
-    }
-    if (hipMemsetAsync(t->zero_arena, 0, t->zero_bytes, st) != hipSuccess) return bail(fail(NGF_E_HIP, "trainer setup failed"));
-    if (hipStreamSynchronize(st) != hipSuccess) return bail(fail(NGF_E_HIP, "trainer setup failed: %s", hipGetErrorString(hipGetLastError())));
-    *out = t;
-    return NGF_OK;
-}
-
-static int tr_grid(const ngf_trainer *t, int64_t items, int per_block, int waves_per_cu = 8)
-{
-    int64_t g = (items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)t->num_cus * waves_per_cu;
-    if (g > cap) g = cap;
-    return g < 1 ? 1 : (int)g;
-}
-
-// What of the step's forks is still open on the aux streams: an error exit of the body must not leave them un-joined to the caller's stream
-// (the next call on that stream would otherwise run beside this one's aux-stream kernels).
-struct ForkState { bool fold = false, chains = false; };
-
-// The step in two parts.  Part A (train_forward_part): everything up to and including the colour forward -- after it the per-sample weights and
-// colours of the batch are in the trainer's buffers.  Part B (train_backward_part): compositing backward, colour backward, the three forked
-// chains.  The fused entry points run A, the fused compositing kernel <0> and B in one call; ngf_train_forward runs A and the compositing
-// kernel <1> (rgb_map / depth_map out), ngf_train_backward_grad the compositing kernel <2> (d loss / d rgb_map in) and B.
-static int train_forward_part(ngf_trainer *t, const float *rays, const float *jitter, int64_t n, int32_t n_samples, int32_t white_bg, int32_t gauge_on,
-                              int64_t *n_active_host, void *hip_stream, ForkState &fs, ngf_trainer::Pending &P)
-{
-    if (n <= 0 || n > t->d.max_rays || n_samples <= 0 || n_samples > t->d.max_samples)
-        return fail(NGF_E_ARG, "ngf_train_backward: n=%lld (max %lld), n_samples=%d (max %d)", (long long)n, (long long)t->d.max_rays, n_samples,
-                    t->d.max_samples);
-    hipStream_t st = (hipStream_t)hip_stream;
-    const ngf_train_desc &d = t->d;
-    P.valid = false;
-    P.T = t->proto;
-    TrainArgs &T = P.T;
-    RenderArgs &A = T.R;
-    A.rays = rays; A.jitter = jitter; A.n = n; A.S = n_samples; A.white_bg = white_bg ? 1 : 0; A.mode = gauge_on ? 1 : 0;
-    T.inv_count = 1.0f / (3.0f * (float)n);
-    A.ablate = knob(KNOB_ABLATE) > 0 ? knob(KNOB_ABLATE) : 0;      // timing experiments only (profiles/exp_train_ablate.sh)
-    if (int prc = poison_lds(st)) return prc;
-    // ngf_debug_set("ablate", 1 << 19) keeps the whole step on the caller's stream (see the forks below)
-    const bool fork = !(A.ablate & (1 << 19));
-    hipStream_t sx = fork ? t->aux[0] : st;
-    ProjectArgs PJ;
-    PJ.wd = d.dens_w;
-    // parameters -> packed textures where the trainer's copy is not current (ngf_train_adam writes the copy along with the parameter;
-    // ngf_train_params_changed marks every copy stale); gradient buffers -> 0
-    for (int p = 0; p < 3; ++p) {
-        const int H = d.plane_h[p], W = d.plane_w[p], gh = d.gauge_h[p], gw = d.gauge_w[p];
-        const size_t tex = (size_t)(H + 2) * (W + 2);
-        if (!t->tex_fresh[p]) {
-            pack_plane_kernel<<<2048, 256, 0, st>>>(d.plane[p], H, W, 0, 16, t->tex_d[p]);
-            pack_plane_kernel<<<2048, 256, 0, st>>>(d.plane[p], H, W, 16, 48, t->tex_a[p]);
-            t->tex_fresh[p] = true;
-        }
-        if (!t->tex_fresh[3 + p]) {
-            pack_plane_kernel<<<256, 256, 0, st>>>(d.gauge[p], gh, gw, 0, 2, t->tex_g[p]);
-            t->tex_fresh[3 + p] = true;
-        }
-        PJ.tex16[p] = t->tex_d[p]; PJ.texels[p] = (int64_t)tex; PJ.q[p] = t->q_d[p];
-    }
-    hipLaunchKernelGGL(train_project_density_kernel, dim3(128, 3), dim3(256), 0, st, PJ);
-    HIP_TRY(hipMemsetAsync(t->zero_arena, 0, t->zero_bytes, st));
-    // the LDS images of the colour MLP are first read by the colour forward: built beside the density kernel and the scan
-    T.fwd_image = t->fwd_image; T.bwd_image = t->bwd_image; T.fwd16_image = t->fwd16_image;
-    if (fork) {
-        HIP_TRY(hipEventRecord(t->ev_fork, st));
-        HIP_TRY(hipStreamWaitEvent(sx, t->ev_fork, 0));
-    }
-    hipLaunchKernelGGL(train_fold_kernel, dim3(48), dim3(256), 0, sx, T, t->fwd_image, t->bwd_image, t->fwd16_image);
-    if (fork) { HIP_TRY(hipEventRecord(t->ev_join[0], sx)); fs.fold = true; }
-
-    const int64_t pairs = n * n_samples;
-    hipLaunchKernelGGL(train_density_kernel, dim3(tr_grid(t, pairs, 256)), dim3(256), 0, st, T);
-    const int ray_blocks = (int)((n + 3) / 4);        // sixteen lanes per ray
-    hipLaunchKernelGGL(train_scan_kernel, dim3(ray_blocks), dim3(64), 0, st, T, 0);
-    // The overflow flag belongs to the path that cannot cut the list into chunks: speculative rows WITHOUT a host count.  A caller that passes
-    // n_active_host gets the chunked path and a complete gradient -- flagging that step would make Adam skip a valid update.
-    const bool spec_rows = t->speculative && !n_active_host;
-    hipLaunchKernelGGL(train_prefix_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)T.count, n, T.offset, spec_rows ? t->chunk : (int64_t)0, t->overflow);
-    // The colour kernels walk the active list.  When one chunk of activation rows holds every sample of the batch (the default:
-    // HBM is sized for it) they read the active count from the device and run with fixed grids -- the stream never waits for the
-    // host.  With a smaller chunk (chunk_samples of the descriptor) the count comes to the host to cut the list into chunks.
-    const bool no_sync = (t->chunk >= pairs || t->speculative) && !n_active_host;
-    int32_t n_active = 0;
-    if (!no_sync) {
-        HIP_TRY(hipMemcpyAsync(&n_active, T.offset + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (n_active_host) *n_active_host = n_active;
-    }
-    hipLaunchKernelGGL(train_scan_kernel, dim3(ray_blocks), dim3(64), 0, st, T, 1);
-
-    const size_t lds_f = (size_t)(((kFwdImage + 3) & ~3) + kTrainWaves * kFwdTileFloats) * sizeof(float),
-                 lds_b = (size_t)(((kBwdImage + 3) & ~3) + kTrainWavesBwd * kBwdTileFloats) * sizeof(float);
-    static_assert((((kFwdImage + 3) & ~3) + kTrainWaves * kFwdTileFloats) * 4 <= 160 * 1024, "colour forward LDS");
-    static_assert((((kBwdImage + 3) & ~3) + kTrainWavesBwd * kBwdTileFloats) * 4 <= 160 * 1024, "colour backward LDS");
-    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(train_color_fwd_kernel), lds_f));
-    const size_t lds_f16 = (size_t)((MlpLayout16<48>::TOTAL + 3) & ~3) * sizeof(float);
-    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(train_color_fwd16_kernel), lds_f16));
-    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(train_color_bwd_kernel), lds_b));
-    if (fork) { HIP_TRY(hipStreamWaitEvent(st, t->ev_join[0], 0)); fs.fold = false; }          // the images
-    const int32_t *cnt = no_sync ? T.offset + n : nullptr;
-    T.n_active_dev = cnt;
-    // upper bound of the list length the loops below are sized for (speculative rows: what the trainer keeps rows for -- the kernels stop at
-    // min(that, the device's count); a longer list is flagged, train_prefix_kernel)
-    const int64_t list_len = no_sync ? std::min<int64_t>(pairs, t->chunk) : n_active;
-    const bool single = list_len <= t->chunk;
-    // colour forward over the whole list (activations kept when the list fits one chunk)
-    for (int64_t base = 0; base < list_len; base += t->chunk) {
-        T.chunk_base = (int32_t)base;
-        T.chunk_n = (int32_t)std::min<int64_t>(t->chunk, list_len - base);
-        T.store = single ? 1 : 0;
-        // round 5: the colour forward in the eval pass's shape (twelve waves per CU, rows stored from registers); ngf_debug_set("ablate", 1 << 23) = the LDS-tile kernel (A/B)
-        if (A.ablate & (1 << 23)) hipLaunchKernelGGL(train_color_fwd_kernel, dim3(tr_grid(t, (T.chunk_n + 15) / 16, kTrainWaves, 1)), dim3(kTrainWaves * 64), lds_f, st, T);
-        else hipLaunchKernelGGL(train_color_fwd16_kernel, dim3(tr_grid(t, (T.chunk_n + 15) / 16, kTrainWaves16, 1)), dim3(kTrainWaves16 * 64), lds_f16, st, T);
-    }
-    P.fork = fork; P.no_sync = no_sync; P.single = single; P.n = n; P.n_samples = n_samples; P.list_len = list_len;
-    P.valid = true;
-    HIP_TRY(hipGetLastError());
-    return NGF_OK;
-}
-
-static inline dim3 comp_grid(int64_t n) { return dim3((unsigned)((n + 64 / kCompLanes - 1) / (64 / kCompLanes))); }
-
-// Part B; the compositing kernel of the calling form has run on hip_stream.  rgb_loss may be NULL (no loss is delivered).
-static int train_backward_part(ngf_trainer *t, ngf_trainer::Pending &P, double *rgb_loss, int32_t loss_len, void *hip_stream, ForkState &fs)
-{
-    hipStream_t st = (hipStream_t)hip_stream;
-    const ngf_train_desc &d = t->d;
-    TrainArgs &T = P.T;
-    RenderArgs &A = T.R;
-    (void)A;
-    const bool fork = P.fork, no_sync = P.no_sync, single = P.single;
-    const int64_t n = P.n, list_len = P.list_len;
-    const int32_t n_samples = P.n_samples;
-    hipStream_t sx = fork ? t->aux[0] : st, sb = fork ? t->aux[1] : st;
-    const size_t lds_f = (size_t)(((kFwdImage + 3) & ~3) + kTrainWaves * kFwdTileFloats) * sizeof(float),
-                 lds_b = (size_t)(((kBwdImage + 3) & ~3) + kTrainWavesBwd * kBwdTileFloats) * sizeof(float);
-    const int32_t *cnt = no_sync ? T.offset + n : nullptr;
-    const dim3 dgrid(tr_grid(t, n * ((n_samples + 63) / 64), 4, knob(KNOB_TRAIN_DWG) > 0 ? knob(KNOB_TRAIN_DWG) : kDensBwdGroupsPerCu + 1));          // knob train_dwg (sweeps): workgroups per CU
-    // After the colour backward of a chunk the step forks: the weight-gradient GEMMs (sx) and the colour-plane scatter (sb) leave the
-    // caller's stream, which goes on with the density / gauge backward and waits for both before it returns to the caller's order.  None of
-    // these chains fills the device alone (LDS transposes, LDS latency, the atomic unit).  (Tried: the density / gauge backward beside the
-    // colour backward, with the colour path's d loss / d t scattered into the gauge planes by a kernel of its own -- the active entries of a
-    // ray span the whole plane, their scatter cannot be merged in LDS, and the step got 0.17 ms slower.)
-    auto join = [&]() -> int {
-        if (fork && fs.chains) {
-            HIP_TRY(hipStreamWaitEvent(st, t->ev_join[0], 0));
-            HIP_TRY(hipStreamWaitEvent(st, t->ev_join[1], 0));
-        }
-        fs.chains = false;
-        return NGF_OK;
-    };
-    for (int64_t base = 0; base < list_len; base += t->chunk) {
-        T.chunk_base = (int32_t)base;
-        T.chunk_n = (int32_t)std::min<int64_t>(t->chunk, list_len - base);
-        const int passes = (T.chunk_n + 15) / 16;
-        if (int jrc = join()) return jrc;              // the previous chunk's chains read the rows this chunk overwrites
-        if (!single) {
-            T.store = 1;
-            if (A.ablate & (1 << 23)) hipLaunchKernelGGL(train_color_fwd_kernel, dim3(tr_grid(t, passes, kTrainWaves, 1)), dim3(kTrainWaves * 64), lds_f, st, T);
-            else hipLaunchKernelGGL(train_color_fwd16_kernel, dim3(tr_grid(t, passes, kTrainWaves16, 1)), dim3(kTrainWaves16 * 64), (size_t)((MlpLayout16<48>::TOTAL + 3) & ~3) * sizeof(float), st, T);
-        }
-        T.bin_accumulate = base > 0 ? 1 : 0;
-        if (base > 0) HIP_TRY(hipMemsetAsync(T.bin_count, 0, ((size_t)T.nbins + 1) * sizeof(int32_t), st));      // the first chunk's counters: the zero arena
-        hipLaunchKernelGGL(train_color_bwd_kernel, dim3(tr_grid(t, passes, kTrainWavesBwd, 1)), dim3(kTrainWavesBwd * 64), lds_b, st, T);
-        // colour-plane scatter: order the chunk's (plane, sample) pairs by bin, then one wave per unit (ngf_train.hpp section 5b); the
-        // single-workgroup prefix stays on this stream, ahead of the fork (beside three full-device kernels it took 0.13 ms instead of 0.01)
-        hipLaunchKernelGGL(train_bin_prefix_kernel, dim3(1), dim3(1024), 0, st, T);
-        if (fork) {
-            HIP_TRY(hipEventRecord(t->ev_fork, st));
-            HIP_TRY(hipStreamWaitEvent(sb, t->ev_fork, 0));
-            HIP_TRY(hipStreamWaitEvent(sx, t->ev_fork, 0));
-        }
-        hipLaunchKernelGGL(train_bin_perm_kernel, dim3(tr_grid(t, 3 * (int64_t)T.chunk_n, 256)), dim3(256), 0, sb, T);
-#ifdef NGF_EXPERIMENTS
-        if (A.ablate & (1 << 18)) hipLaunchKernelGGL(train_bin_scatter_mfma_kernel, dim3(3 * t->num_cus), dim3(256), 0, sb, T);      // the matrix-pipe version (slower)
-        else
-#endif
-        hipLaunchKernelGGL(train_bin_scatter_kernel, dim3(2 * t->num_cus), dim3(256), 0, sb, T);
-        {   // one (texel, channel) per thread and two dependent loads each: as many workgroups as the largest plane has items (a few per thread
-            // left the kernel waiting on memory latency: 40 us -> see profiles/r03_train_R1_kernel_stats.txt)
-            int64_t items = 0;
-            for (int p = 0; p < 3; ++p) items = std::max<int64_t>(items, (int64_t)(d.plane_h[p] + 2) * (d.plane_w[p] + 2) * 48);
-            const int gx = (int)std::min<int64_t>((items + 255) / 256, (int64_t)64 * t->num_cus);
-            hipLaunchKernelGGL(train_bin_gather_kernel, dim3(gx, 3), dim3(256), 0, sb, T);
-        }
-        const int rows = T.chunk_n;
-        int xg = (rows + 31) / 32;                      // 32-sample chunks; at most two workgroups per CU walk them
-        if (xg > 2 * t->num_cus) xg = 2 * t->num_cus;
-        // heaviest first: M = Delta1^T F (train_unfold_kernel turns it into d W1[:, :144] and d basis), d W2, the 15 view columns of d W1, d W3
-        XtyAll G;
-        G.X[0] = T.D1; G.ldx[0] = 64; G.Y[0] = T.F;  G.ldy[0] = 144; G.mvalid[0] = 64; G.nvalid[0] = 144; G.out[0] = T.M; G.ldo[0] = 144;
-        G.X[1] = T.D2; G.ldx[1] = 64; G.Y[1] = T.H1; G.ldy[1] = 64;  G.mvalid[1] = 64; G.nvalid[1] = 64;  G.out[1] = t->g_dense[TP_W2]; G.ldo[1] = 64;
-        G.X[2] = T.D1; G.ldx[2] = 64; G.Y[2] = T.V;  G.ldy[2] = 16;  G.mvalid[2] = 64; G.nvalid[2] = 15;  G.out[2] = t->g_dense[TP_W1] + 144; G.ldo[2] = 159;
-        G.X[3] = T.D3; G.ldx[3] = 16; G.Y[3] = T.H2; G.ldy[3] = 64;  G.mvalid[3] = 3;  G.nvalid[3] = 64;  G.out[3] = t->g_dense[TP_W3]; G.ldo[3] = 64;
-        G.rows = rows; G.rows_dev = cnt;
-        hipLaunchKernelGGL(xty_all_kernel, dim3(xg, 4), dim3(256), 0, sx, G);
-        if (base + t->chunk >= list_len) hipLaunchKernelGGL(train_unfold_kernel, dim3(96), dim3(256), 0, sx, T, t->g_dense[TP_W1], t->g_dense[TP_BASIS]);
-        if (fork) {
-            // both events are recorded before an error can return: the wrapper's rescue join waits on events of THIS step
-            const hipError_t e0 = hipEventRecord(t->ev_join[0], sx), e1 = hipEventRecord(t->ev_join[1], sb);
-            fs.chains = true;
-            HIP_TRY(e0);
-            HIP_TRY(e1);
-        }
-    }
-    if (list_len <= 0) {        // no active sample and the host knows it: nothing wrote the colour planes' gradients
-        for (int p = 0; p < 3; ++p) HIP_TRY(hipMemsetAsync(t->g_a[p], 0, (size_t)(d.plane_h[p] + 2) * (d.plane_w[p] + 2) * 48 * sizeof(float), st));
-        hipLaunchKernelGGL(train_unfold_kernel, dim3(96), dim3(256), 0, st, T, t->g_dense[TP_W1], t->g_dense[TP_BASIS]);
-    }
-    // (Tried: the D_p share <true, false> beside the colour backward and the gauge share <false, true> after it -- each half takes as long
-    // as the whole, 0.31 ms: the kernel is bound by the dependent chain of an item, not by what it scatters.)
-    hipLaunchKernelGGL((train_density_bwd_kernel<true, true>), dgrid, dim3(256), 0, st, T);
-    UnblockArgs U;
-    FinishArgs FA;
-    FA.wd = d.dens_w; FA.g_wd = t->g_dense[TP_DENS_W];
-    for (int p = 0; p < 3; ++p) {
-        FA.D[p] = t->d_d[p]; FA.tex16[p] = t->tex_d[p]; FA.w2[p] = d.plane_w[p] + 2; FA.bw[p] = T.d_bw[p];
-        FA.texels[p] = (int64_t)(d.plane_h[p] + 2) * (d.plane_w[p] + 2); FA.g_dens[p] = t->g_d[p];
-        U.src[p] = t->g_gb[p]; U.dst[p] = t->g_g[p]; U.w2[p] = d.gauge_w[p] + 2; U.h2[p] = d.gauge_h[p] + 2; U.bw[p] = T.g_bw[p];
-    }
-    U.g_bd = T.g_bd;
-    U.loss_src = T.loss; U.loss_dst = rgb_loss; U.loss_len = loss_len; U.inv_count = 1.0 / (3.0 * (double)n); U.overflow = t->overflow;        // the loss travels with the last kernel of the caller's stream (a copy of 8 bytes is a launch of its own)
-    hipLaunchKernelGGL(train_density_finish_kernel, dim3(128, 3), dim3(256), 0, st, FA);
-    hipLaunchKernelGGL(train_unblock_gauge_kernel, dim3(128, 3), dim3(256), 0, st, U);
-    if (int jrc = join()) return jrc;
-    HIP_TRY(hipGetLastError());
-    return NGF_OK;
-}
-
-// error exit after a fork: the caller's stream still waits for what the aux streams hold (best effort: the error being reported stands)
-static int rescue_join(ngf_trainer *t, int rc, const ForkState &fs, void *hip_stream)
-{
-    if (rc != NGF_OK && t && (fs.fold || fs.chains)) {
-        hipStream_t st = (hipStream_t)hip_stream;
-        (void)hipStreamWaitEvent(st, t->ev_join[0], 0);
-        if (fs.chains) (void)hipStreamWaitEvent(st, t->ev_join[1], 0);
-    }
-    return rc;
-}
-
-static int train_backward_joined(ngf_trainer *t, const float *rays, const float *rgb_train, const float *jitter, int64_t n, int32_t n_samples,
-                                 int32_t white_bg, int32_t gauge_on, double *rgb_loss, int32_t loss_len, int64_t *n_active_host, void *hip_stream)
-{
-    if (!t || !rays || !rgb_train || !rgb_loss) return fail(NGF_E_ARG, "ngf_train_backward: null argument");
-    if (loss_len < 1) return fail(NGF_E_ARG, "ngf_train_backward2: loss_len=%d (1 = the sum of squared residuals, 2 = sum and mean)", loss_len);
-    ForkState fs;
-    ngf_trainer::Pending P;                 // the fused call keeps its state to itself: a pending ngf_train_forward is not disturbed ...
-    t->pending.valid = false;               // ... but the trainer's per-sample buffers are: its backward must re-run the forward
-    int rc = train_forward_part(t, rays, jitter, n, n_samples, white_bg, gauge_on, n_active_host, hip_stream, fs, P);
-    if (rc == NGF_OK) {
-        P.T.target = rgb_train;
-        hipLaunchKernelGGL(train_composite_bwd_kernel<0>, comp_grid(n), dim3(64), 0, (hipStream_t)hip_stream, P.T);
-        rc = train_backward_part(t, P, rgb_loss, loss_len, hip_stream, fs);
-    }
-    return rescue_join(t, rc, fs, hip_stream);
-}
-
-// ---- the two-call form: the torch.autograd boundary of Base.forward(is_train=True) (TriPlane/main.py:272-296) -----------------------------
-extern "C" int ngf_train_forward(ngf_trainer *t, const float *rays, const float *jitter, int64_t n, int32_t n_samples, int32_t white_bg,
-                                 int32_t gauge_on, float *rgb_map, float *depth_map, int64_t *n_active_host, int64_t *ticket, void *hip_stream)
-{
-    if (!t || !rays || !rgb_map || !depth_map || !ticket) return fail(NGF_E_ARG, "ngf_train_forward: null argument");
-    ForkState fs;
-    int rc = train_forward_part(t, rays, jitter, n, n_samples, white_bg, gauge_on, n_active_host, hip_stream, fs, t->pending);
-    if (rc == NGF_OK) {
-        t->pending.T.rgb_out = rgb_map; t->pending.T.depth_out = depth_map;
-        hipLaunchKernelGGL(train_composite_bwd_kernel<1>, comp_grid(n), dim3(64), 0, (hipStream_t)hip_stream, t->pending.T);
-        rc = hipGetLastError() == hipSuccess ? NGF_OK : fail(NGF_E_HIP, "ngf_train_forward: launch failed");
-        t->pending.ticket = *ticket = ++t->tickets;
-    }
-    if (rc != NGF_OK) t->pending.valid = false;
-    return rescue_join(t, rc, fs, hip_stream);
-}
-
-extern "C" int ngf_train_backward_grad(ngf_trainer *t, int64_t ticket, const float *d_rgb_map, void *hip_stream)
-{
-    if (!t || !d_rgb_map) return fail(NGF_E_ARG, "ngf_train_backward_grad: null argument");
-    if (!t->pending.valid || t->pending.ticket != ticket)
-        return fail(NGF_E_STALE, "ngf_train_backward_grad: ticket %lld is not the trainer's last forward (%s) -- another forward or a fused step used the "
-                    "trainer's buffers since; run ngf_train_forward again", (long long)ticket, t->pending.valid ? "a newer one is pending" : "none is pending");
-    ForkState fs;
-    ngf_trainer::Pending &P = t->pending;
-    P.T.d_rgb = d_rgb_map;
-    hipLaunchKernelGGL(train_composite_bwd_kernel<2>, comp_grid(P.n), dim3(64), 0, (hipStream_t)hip_stream, P.T);
-    const int rc = train_backward_part(t, P, nullptr, 0, hip_stream, fs);
-    P.valid = false;                        // the gradients are in the trainer's buffers (ngf_train_get_grad); the per-sample state is spent
-    return rescue_join(t, rc, fs, hip_stream);
-}
-
-// ABI 3: the loss buffer's length travels with the call (loss_len = 2: [0] the sum of squared residuals, [1] their mean)
-extern "C" int ngf_train_backward2(ngf_trainer *t, const float *rays, const float *rgb_train, const float *jitter, int64_t n, int32_t n_samples,
-                                   int32_t white_bg, int32_t gauge_on, double *rgb_loss, int32_t loss_len, int64_t *n_active_host, void *hip_stream)
-{
-    return train_backward_joined(t, rays, rgb_train, jitter, n, n_samples, white_bg, gauge_on, rgb_loss, loss_len, n_active_host, hip_stream);
-}
-
-// The ABI-1 entry point keeps the ABI-1 contract: rgb_loss is ONE double (the sum of squared residuals).  (ABI 2 wrote two doubles through
-// this symbol: a caller built against ABI 1 got an 8-byte out-of-bounds device write.)
-extern "C" int ngf_train_backward(ngf_trainer *t, const float *rays, const float *rgb_train, const float *jitter, int64_t n, int32_t n_samples,
-                                  int32_t white_bg, int32_t gauge_on, double *rgb_loss, int64_t *n_active_host, void *hip_stream)
-{
-    return train_backward_joined(t, rays, rgb_train, jitter, n, n_samples, white_bg, gauge_on, rgb_loss, 1, n_active_host, hip_stream);
-}
-
-extern "C" int ngf_train_get_active(ngf_trainer *t, int64_t n, int32_t *out, void *hip_stream)
-{
-    if (!t || !out || n <= 0 || n > t->d.max_rays) return fail(NGF_E_ARG, "ngf_train_get_active: bad argument");
-    HIP_TRY(hipMemcpyAsync(out, t->proto.offset + n, sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
-    return NGF_OK;
-}
-
-extern "C" int ngf_train_get_grad(ngf_trainer *t, int32_t which, float *out, void *hip_stream)
-{
-    if (!t || !out || which < 0 || which >= TP_COUNT) return fail(NGF_E_ARG, "ngf_train_get_grad: bad argument");
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (which < 3) {
-        const int p = which;
-        hipLaunchKernelGGL(unpack_plane_kernel, dim3(1024), dim3(256), 0, st, (const float *)t->g_d[p], 16, (const float *)t->g_a[p], 64, t->d.plane_h[p],
-                           t->d.plane_w[p], out);
-    } else if (which < 6) {
-        const int p = which - 3;
-        hipLaunchKernelGGL(unpack_plane_kernel, dim3(256), dim3(256), 0, st, (const float *)t->g_g[p], 2, (const float *)nullptr, 2, t->d.gauge_h[p],
-                           t->d.gauge_w[p], out);
-    } else {
-        HIP_TRY(hipMemcpyAsync(out, t->g_dense[which], (size_t)t->dense_n[which] * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    HIP_TRY(hipGetLastError());
-    return NGF_OK;
-}
-
-// ABI 5: every requested gradient in ONE call (out[k] NULL = not wanted): three tiled transposes for the planes, the gauge planes, one launch for
-// the nine MLP parameters -- the autograd path (ngf_amd.train.RenderGrad.backward) made fifteen calls of ngf_train_get_grad per step.
-extern "C" int ngf_train_get_grads(ngf_trainer *t, float *const *out, void *hip_stream)
-{
-    if (!t || !out) return fail(NGF_E_ARG, "ngf_train_get_grads: null argument");
-    hipStream_t st = (hipStream_t)hip_stream;
-    for (int p = 0; p < 3; ++p) {
-        if (out[p]) {
-            const int H = t->d.plane_h[p], W = t->d.plane_w[p];
-            hipLaunchKernelGGL((unpack_plane_tiled_kernel<64, 16>), dim3(H * ((W + 63) / 64)), dim3(256), 0, st, (const float *)t->g_d[p], (const float *)t->g_a[p], H, W, out[p]);
-        }
-        if (out[3 + p])
-            hipLaunchKernelGGL(unpack_plane_kernel, dim3(256), dim3(256), 0, st, (const float *)t->g_g[p], 2, (const float *)nullptr, 2, t->d.gauge_h[p], t->d.gauge_w[p], out[3 + p]);
-    }
-    CopyDenseAll D;
-    int32_t at = 0;
-    for (int j = 0; j < kDenseParams; ++j) {
-        const int k = TP_DENS_W + j;
-        D.src[j] = t->g_dense[k]; D.dst[j] = out[k]; D.begin[j] = at;
-        if (out[k]) at += (int32_t)t->dense_n[k];
-    }
-    D.begin[kDenseParams] = at;
-    if (at > 0) hipLaunchKernelGGL(copy_dense_all_kernel, dim3((at + 255) / 256), dim3(256), 0, st, D);
-    HIP_TRY(hipGetLastError());
-    return NGF_OK;
-}
-
-// ABI 5: torch.optim.Adam's update for the trainer's fifteen parameters from the CALLER'S gradient tensors and moments (reference layouts: what
-// p.grad, state['exp_avg'], state['exp_avg_sq'] are after total_loss.backward()), planes in one pass that also writes the trainer's packed
-// copy -- the next ngf_train_forward reads it without a re-pack.  step_count[k] <= 0 or grad[k] NULL = parameter k is left alone.  The arithmetic
-// is ngf_train_adam's (adam_one); no L1 term is added here: the caller's loss put it into the gradient.  Works on trainers with or without
-// their own moments.  ngf_amd.optim.Adam is the Python face (TriPlane/main.py:234-242,294-302 unchanged).
-extern "C" int ngf_train_adam_ext(ngf_trainer *t, const float *const *grad, float *const *exp_avg, float *const *exp_avg_sq, const int32_t *step_count,
-                                  const float *lr, float beta1, float beta2, float eps, void *hip_stream)
-{
-    if (!t || !grad || !exp_avg || !exp_avg_sq || !step_count || !lr) return fail(NGF_E_ARG, "ngf_train_adam_ext: null argument");
-    const ngf_train_desc &d = t->d;
-    hipStream_t st = (hipStream_t)hip_stream;
-    auto args = [&](int k) {
-        AdamArgs a;
-        a.lr = lr[k]; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.l1 = 0.0f;
-        a.bc1 = (float)(1.0 - pow((double)beta1, (double)step_count[k]));
-        a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step_count[k]));
-        return a;
-    };
-    for (int k = 0; k < TP_COUNT; ++k)
-        if (step_count[k] > 0 && grad[k] && (!exp_avg[k] || !exp_avg_sq[k])) return fail(NGF_E_ARG, "ngf_train_adam_ext: parameter %d has a gradient but no moments", k);
-    const bool fork = !(knob(KNOB_ABLATE) > 0 && (knob(KNOB_ABLATE) & (1 << 19)));
-    const bool big[3] = {step_count[0] > 0 && grad[0], step_count[1] > 0 && grad[1], step_count[2] > 0 && grad[2]};
-    const bool forked = fork && (big[1] || big[2]);
-    if (forked) {
-        HIP_TRY(hipEventRecord(t->ev_fork, st));
-        HIP_TRY(hipStreamWaitEvent(t->aux[0], t->ev_fork, 0));
-        HIP_TRY(hipStreamWaitEvent(t->aux[1], t->ev_fork, 0));
-    }
-    for (int p : {1, 2, 0}) {
-        if (!big[p]) continue;
-        const int H = d.plane_h[p], W = d.plane_w[p];
-        hipStream_t sk = (forked && p > 0) ? t->aux[p - 1] : st;
-        // a stale packed copy (ngf_train_params_changed since the last forward) is simply rewritten: the kernel stores every interior texel and the
-        // zero border was written when the copy was first packed
-        hipLaunchKernelGGL((adam_plane_kernel<64, 16, true>), dim3(H * ((W + 63) / 64)), dim3(256), 0, sk, d.plane[p], exp_avg[p], exp_avg_sq[p], H, W,
-                           (const float *)nullptr, (const float *)nullptr, t->tex_d[p], t->tex_a[p], args(p), (const int32_t *)nullptr, grad[p]);
-        t->tex_fresh[p] = true;
-    }
-    for (int p = 0; p < 3; ++p) {
-        const int k = 3 + p;
-        if (!(step_count[k] > 0 && grad[k])) continue;
-        hipLaunchKernelGGL((adam_plane_kernel<2, 2, true>), dim3(d.gauge_h[p] * ((d.gauge_w[p] + 63) / 64)), dim3(256), 0, st, d.gauge[p], exp_avg[k], exp_avg_sq[k],
-                           d.gauge_h[p], d.gauge_w[p], (const float *)nullptr, (const float *)nullptr, t->tex_g[p], (float *)nullptr, args(k), (const int32_t *)nullptr, grad[k]);
-        t->tex_fresh[k] = true;
-    }
-    float *params[TP_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d.dens_w, d.dens_b, d.basis, d.w1, d.b1, d.w2, d.b2, d.w3, d.b3};
-    AdamDenseAll D;
-    int32_t at = 0;
-    for (int j = 0; j < kDenseParams; ++j) {
-        const int k = TP_DENS_W + j;
-        D.p[j] = params[k]; D.m[j] = exp_avg[k]; D.v[j] = exp_avg_sq[k]; D.g[j] = grad[k];
-        D.begin[j] = at;
-        D.a[j] = args(k);
-        if (step_count[k] > 0 && grad[k]) at += (int32_t)t->dense_n[k];
-        else { D.a[j].bc1 = 1.0f; D.a[j].bc2_sqrt = 1.0f; }          // empty segment
-    }
-    D.begin[kDenseParams] = at;
-    D.skip = nullptr;
-    if (at > 0) hipLaunchKernelGGL(adam_dense_all_kernel, dim3((at + 255) / 256), dim3(256), 0, st, D);
-    if (forked)
-        for (int j = 0; j < 2; ++j) {
-            HIP_TRY(hipEventRecord(t->ev_join[j], t->aux[j]));
-            HIP_TRY(hipStreamWaitEvent(st, t->ev_join[j], 0));
-        }
-    HIP_TRY(hipGetLastError());
-    return NGF_OK;
-}
-
-extern "C" int ngf_train_adam(ngf_trainer *t, int32_t which, int32_t step_count, float lr, float beta1, float beta2, float eps, float l1_weight,
-                              void *hip_stream)
-{
-    if (!t || which < 0 || which >= TP_COUNT || step_count < 1) return fail(NGF_E_ARG, "ngf_train_adam: bad argument");
-    if (!t->has_adam) return fail(NGF_E_ARG, "ngf_train_adam: the trainer was made without Adam moments (ngf_train_desc.exp_avg / exp_avg_sq all NULL)");
-    hipStream_t st = (hipStream_t)hip_stream;
-    const ngf_train_desc &d = t->d;
-    AdamArgs a;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step_count));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step_count));
-    a.l1 = 0.0f;
-    if (which < 3) {
-        const int p = which, H = d.plane_h[p], W = d.plane_w[p];
-        a.l1 = l1_weight / (float)((int64_t)64 * H * W);             // d/dp of l1_weight * mean(|p|)
-        if (!t->tex_fresh[p]) return fail(NGF_E_ARG, "ngf_train_adam: the planes changed (ngf_train_params_changed) and no backward has re-packed them");
-        hipLaunchKernelGGL((adam_plane_kernel<64, 16>), dim3(H * ((W + 63) / 64)), dim3(256), 0, st, d.plane[p], d.exp_avg[which], d.exp_avg_sq[which], H, W,
-                           (const float *)t->g_d[p], (const float *)t->g_a[p], t->tex_d[p], t->tex_a[p], a, (const int32_t *)t->overflow);
-    } else if (which < 6) {
-        const int p = which - 3;
-        if (!t->tex_fresh[which]) return fail(NGF_E_ARG, "ngf_train_adam: the planes changed (ngf_train_params_changed) and no backward has re-packed them");
-        hipLaunchKernelGGL((adam_plane_kernel<2, 2>), dim3(d.gauge_h[p] * ((d.gauge_w[p] + 63) / 64)), dim3(256), 0, st, d.gauge[p], d.exp_avg[which],
-                           d.exp_avg_sq[which], d.gauge_h[p], d.gauge_w[p], (const float *)t->g_g[p], (const float *)nullptr, t->tex_g[p], (float *)nullptr, a, (const int32_t *)t->overflow);
-    } else {
-        float *params[TP_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d.dens_w, d.dens_b, d.basis, d.w1, d.b1, d.w2, d.b2, d.w3, d.b3};
-        hipLaunchKernelGGL(adam_dense_kernel, dim3(64), dim3(256), 0, st, params[which], (const float *)t->g_dense[which], d.exp_avg[which],
-                           d.exp_avg_sq[which], t->dense_n[which], a, (const int32_t *)t->overflow);
-    }
-    HIP_TRY(hipGetLastError());
-    return NGF_OK;
-}
-
-// Speculative rows (ngf_train_desc::chunk_samples < 0): how many steps since the trainer was made had more active samples than activation rows
-// (their Adam updates were skipped on the device) and the trainer's row count.  Synchronises the stream.
-extern "C" int ngf_train_overflow_count(ngf_trainer *t, int64_t *count_host, int64_t *rows_host, void *hip_stream)
-{
-    if (!t || !count_host) return fail(NGF_E_ARG, "ngf_train_overflow_count: null argument");
-    int32_t v[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(v, t->overflow, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
-    *count_host = v[1];
-    if (rows_host) *rows_host = t->chunk;
-    return NGF_OK;
-}
-
-// debug: the section clocks of the colour backward (ngf_debug_set("ablate", 1 << 20)), summed over waves since the last call
-extern "C" int ngf_train_debug_sections(ngf_trainer *t, uint64_t *out16)
-{
-    if (!t || !out16) return fail(NGF_E_ARG, "ngf_train_debug_sections: null argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out16, t->proto.prof, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(t->proto.prof, 0, 16 * sizeof(uint64_t)));
-    return NGF_OK;
-}
-
-extern "C" int ngf_train_params_changed(ngf_trainer *t)
-{
-    if (!t) return fail(NGF_E_ARG, "ngf_train_params_changed: null trainer");
-    for (bool &f : t->tex_fresh) f = false;
-    return NGF_OK;
-}
-
-extern "C" int ngf_train_adam_all(ngf_trainer *t, const int32_t *step_count, const float *lr, float beta1, float beta2, float eps, float l1_weight,
-                                  void *hip_stream)
-{
-    if (!t || !step_count || !lr) return fail(NGF_E_ARG, "ngf_train_adam_all: null argument");
-    const ngf_train_desc &d = t->d;
-    // the three (plane, gauge plane) pairs are independent streams of reads and writes, none of which reaches the HBM rate alone: planes 1
-    // and 2 go to the trainer's own streams (ablate bit 1 << 19: all on the caller's)
-    hipStream_t st = (hipStream_t)hip_stream;
-    const bool fork = !(knob(KNOB_ABLATE) > 0 && (knob(KNOB_ABLATE) & (1 << 19)));
-    if (fork) {
-        HIP_TRY(hipEventRecord(t->ev_fork, st));
-        HIP_TRY(hipStreamWaitEvent(t->aux[0], t->ev_fork, 0));
-        HIP_TRY(hipStreamWaitEvent(t->aux[1], t->ev_fork, 0));
-    }
-    // planes 1 and 2 leave first; the caller's stream takes the small updates (gauge planes, the MLP parameters below) and plane 0
-    for (int k : {1, 2, 3, 4, 5})
-        if (step_count[k] > 0) {
-            hipStream_t sk = (fork && (k == 1 || k == 2)) ? t->aux[k - 1] : st;
-            const int rc = ngf_train_adam(t, k, step_count[k], lr[k], beta1, beta2, eps, l1_weight, (void *)sk);
-            if (rc != NGF_OK) return rc;
-        }
-    float *params[TP_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d.dens_w, d.dens_b, d.basis, d.w1, d.b1, d.w2, d.b2, d.w3, d.b3};
-    AdamDenseAll D;
-    int32_t at = 0;
-    for (int j = 0; j < kDenseParams; ++j) {
-        const int k = TP_DENS_W + j;
-        D.p[j] = params[k]; D.m[j] = d.exp_avg[k]; D.v[j] = d.exp_avg_sq[k]; D.g[j] = t->g_dense[k];
-        D.begin[j] = at;
-        AdamArgs &a = D.a[j];
-        a.lr = lr[k]; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.l1 = 0.0f; a.bc1 = 1.0f; a.bc2_sqrt = 1.0f;
-        if (step_count[k] > 0) {
-            a.bc1 = (float)(1.0 - pow((double)beta1, (double)step_count[k]));
-            a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step_count[k]));
-            at += (int32_t)t->dense_n[k];
-        }
-    }
-    D.begin[kDenseParams] = at;
-    D.skip = t->overflow;
-    if (at > 0) hipLaunchKernelGGL(adam_dense_all_kernel, dim3((at + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, D);
-    if (step_count[0] > 0) {
-        const int rc = ngf_train_adam(t, 0, step_count[0], lr[0], beta1, beta2, eps, l1_weight, hip_stream);
-        if (rc != NGF_OK) return rc;
-    }
-    if (fork) {
-        for (int j = 0; j < 2; ++j) {
-            HIP_TRY(hipEventRecord(t->ev_join[j], t->aux[j]));
-            HIP_TRY(hipStreamWaitEvent(st, t->ev_join[j], 0));
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return NGF_OK;
-}
-

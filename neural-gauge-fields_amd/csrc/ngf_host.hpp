@@ -59,6 +59,36 @@ struct DeviceScope {
     ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
 };
 
+// The device buffers of a trainer handle: every hipMalloc remembered and counted, all freed together (on the CURRENT device: destroy holds a
+// DeviceScope).  `slack`: bytes added to every request that `bytes` does not count; `zero_bytes`: what a zero-byte request (and only that) is rounded up to
+// and counted as.  The TriPlane trainer is {64, 0}, the InfoInv and UV-Mapping trainers are {0, 16}: what ngf_*_trainer_bytes report depends on it.
+struct DeviceAllocs {
+    size_t slack = 0, zero_bytes = 0;
+    std::vector<void *> ptrs;
+    int64_t bytes = 0;
+    DeviceAllocs(size_t slack_, size_t zero_bytes_) : slack(slack_), zero_bytes(zero_bytes_) {}
+
+    template <typename T>
+    int alloc(T **p, size_t count)
+    {
+        const size_t want = count ? count * sizeof(T) : zero_bytes;
+        void *q = nullptr;
+        *p = nullptr;
+        if (hipMalloc(&q, want + slack) != hipSuccess) return fail(NGF_E_HIP, "hipMalloc(%zu bytes) failed for a trainer", want);
+        ptrs.push_back(q);
+        bytes += (int64_t)want;
+        *p = (T *)q;
+        return NGF_OK;
+    }
+    // frees what was allocated after the state (ptrs.size(), bytes) was read; free_all: everything
+    void free_to(size_t mark, int64_t bytes_mark)
+    {
+        while (ptrs.size() > mark) { (void)hipFree(ptrs.back()); ptrs.pop_back(); }
+        bytes = bytes_mark;
+    }
+    void free_all() { free_to(0, 0); }
+};
+
 // device -> host copy of n floats (weights are folded / packed on the host at create time)
 inline int d2h(std::vector<float> &dst, const float *src, size_t n, hipStream_t st)
 {

@@ -10,9 +10,10 @@
 //   ii_mm_reduce_kernel     partials added in chunk order in fp64 (only the chunks that hold rows: the count is read on the device)
 //   ii_adam_plane_kernel    torch.optim.Adam on a plane in one pass: fixed-point accumulator and device-side scale in, + the L1 term, parameter,
 //                           both moments and the packed channel-last copy out
-//   ii_adam_dense_kernel    the thirteen decoder tensors in one launch
+//   adam_dense_all_kernel   the thirteen decoder tensors in one launch (<kIiDense>, ngf_adam.hpp)
 // No float atomics anywhere: two steps from one state give identical bits.
 #pragma once
+#include "ngf_adam.hpp"
 #include "ngf_infoinv_train.hpp"
 
 namespace ngf {
@@ -215,29 +216,14 @@ __global__ void __launch_bounds__(256) ii_plane_grad_add_kernel(const unsigned l
     }
 }
 
-// ---- torch.optim.Adam (betas, eps; no weight decay, no amsgrad), float32, element for element ---------------------------------------------
-struct IiAdam {
-    float lr, beta1, beta2, eps;
-    float bc1, bc2_sqrt;       // 1 - beta1^t, sqrt(1 - beta2^t)
-    float l1;                  // planes: L1_reg_weight / numel, added as l1 * sign(p); 0 otherwise
-};
-
-__device__ __forceinline__ float ii_adam_one(float p, float g, float &m, float &v, const IiAdam &a)
-{
-    m = m + (1.0f - a.beta1) * (g - m);                   // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * a.beta2 + ((1.0f - a.beta2) * g) * g;         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
-    const float step = a.lr / a.bc1;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    return p - step * (m / denom);
-}
-
+// ---- torch.optim.Adam: the planes (AdamArgs, adam_one and the dense kernel adam_dense_all_kernel<kIiDense>: ngf_adam.hpp) --------------------------
 // A plane [96][H][W].  FIXED: the gradient is the fixed-point accumulator [texel][96] times 1 / scale (a NaN scale -- non-finite feature
 // gradients -- gives NaN gradients, never wrapped integers); else `gext`, a float gradient in the parameter's own layout.  A workgroup takes
 // 64 texels of one row: the accumulator rows go through LDS so that every global access is a contiguous run, and the new values leave
 // the same way into the packed copy `tex` -- the next forward packs nothing.
 template <bool FIXED>
 __global__ void __launch_bounds__(256) ii_adam_plane_kernel(float *p, float *m, float *v, int H, int W, const unsigned long long *gacc, const double *bound,
-                                                            const float *gext, float *tex, const IiAdam a)
+                                                            const float *gext, float *tex, const AdamArgs a)
 {
     constexpr int C = kIiC;
     __shared__ float sg[64 * (C + 1)];
@@ -259,7 +245,7 @@ __global__ void __launch_bounds__(256) ii_adam_plane_kernel(float *p, float *m, 
                 const float pv = p[i];
                 const float g = (FIXED ? sg[x * (C + 1) + c] : gext[i]) + a.l1 * (pv > 0.0f ? 1.0f : (pv < 0.0f ? -1.0f : 0.0f));
                 float mi = m[i], vi = v[i];
-                const float pn = ii_adam_one(pv, g, mi, vi, a);
+                const float pn = adam_one(pv, g, mi, vi, a);
                 p[i] = pn; m[i] = mi; v[i] = vi;
                 sg[x * (C + 1) + c] = pn;
             }
@@ -267,28 +253,6 @@ __global__ void __launch_bounds__(256) ii_adam_plane_kernel(float *p, float *m, 
         __syncthreads();
         for (int e = threadIdx.x; e < nx * C; e += 256) tex[texel0 * C + e] = sg[(e / C) * (C + 1) + e % C];
         __syncthreads();
-    }
-}
-
-// every decoder tensor in one launch: segment k = elements [begin[k], begin[k+1]) of the concatenation, each with its own step count / lr
-struct IiAdamDense {
-    float *p[kIiDense], *m[kIiDense], *v[kIiDense];
-    const float *g[kIiDense];
-    int32_t begin[kIiDense + 1];               // begin[k+1] == begin[k] for a skipped parameter
-    IiAdam a[kIiDense];
-};
-
-__global__ void __launch_bounds__(256) ii_adam_dense_kernel(const IiAdamDense D)
-{
-    const int total = D.begin[kIiDense];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        int k = 0;
-#pragma unroll
-        for (int j = 1; j < kIiDense; ++j) k += (i >= D.begin[j]) ? 1 : 0;
-        const int e = i - D.begin[k];
-        float mi = D.m[k][e], vi = D.v[k][e];
-        D.p[k][e] = ii_adam_one(D.p[k][e], D.g[k][e], mi, vi, D.a[k]);
-        D.m[k][e] = mi; D.v[k][e] = vi;
     }
 }
 

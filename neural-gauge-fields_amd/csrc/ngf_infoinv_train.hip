@@ -12,8 +12,7 @@ struct ngf_infoinv_trainer {
     int64_t max_rays = 0;
     int32_t max_samples = 0;
     int64_t cap = 0;                                   // max_rays * max_samples
-    std::vector<void *> allocs;
-    int64_t bytes = 0;
+    DeviceAllocs mem{0, 16};                           // every device buffer of the handle
     float *tex[3] = {nullptr, nullptr, nullptr};       // packed planes
     unsigned long long *gacc[3] = {nullptr, nullptr, nullptr};
     uint8_t *mask = nullptr;
@@ -37,31 +36,6 @@ struct ngf_infoinv_trainer {
 };
 
 namespace {
-
-int ii_alloc(ngf_infoinv_trainer *t, void **p, size_t bytes)
-{
-    *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    HIP_TRY(hipMalloc(p, bytes));
-    t->allocs.push_back(*p);
-    t->bytes += (int64_t)bytes;
-    return NGF_OK;
-}
-
-template <typename T>
-int ii_alloc_n(ngf_infoinv_trainer *t, T **p, size_t n)
-{
-    void *v = nullptr;
-    int rc = ii_alloc(t, &v, n * sizeof(T));
-    *p = (T *)v;
-    return rc;
-}
-
-void ii_free(ngf_infoinv_trainer *t)
-{
-    for (void *p : t->allocs) (void)hipFree(p);
-    t->allocs.clear();
-}
 
 // the parameter tensors in `which` order (include/ngf.h) and their element counts
 void ii_params(const ngf_infoinv_train_desc &d, const float *p[NGF_INFOINV_TRAIN_PARAMS], int64_t n[NGF_INFOINV_TRAIN_PARAMS])
@@ -141,15 +115,6 @@ int ii_mm(ngf_infoinv_trainer *t, const float *X, const float *Y, int64_t rows_c
     return NGF_OK;
 }
 
-IiAdam ii_adam_args(int32_t step, float lr, float beta1, float beta2, float eps, float l1)
-{
-    IiAdam a;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.l1 = l1;
-    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-    return a;
-}
-
 // grad NULL: the trainer's own gradients of the last fused backward (+ the L1 term on the planes); else the caller's tensors
 int ii_adam(ngf_infoinv_trainer *t, const float *const *grad, float *const *m, float *const *v, const int32_t *step_count, const float *lr, float beta1,
             float beta2, float eps, float l1_weight, hipStream_t st)
@@ -164,7 +129,7 @@ int ii_adam(ngf_infoinv_trainer *t, const float *const *grad, float *const *m, f
     for (int p = 0; p < 3; ++p) {
         if (!on(p)) continue;
         const int H = d.plane_h[p], W = d.plane_w[p];
-        const IiAdam a = ii_adam_args(step_count[p], lr[p], beta1, beta2, eps, grad ? 0.0f : l1_weight / (float)((int64_t)kIiC * H * W));
+        const AdamArgs a = adam_args(step_count[p], lr[p], beta1, beta2, eps, grad ? 0.0f : l1_weight / (float)((int64_t)kIiC * H * W));
         const dim3 g(H * ((W + 63) / 64));
         // a stale packed copy is simply rewritten; its zero border is written whenever the forward packs (t->packed unset)
         if (!grad && t->planes_fixed)
@@ -175,18 +140,19 @@ int ii_adam(ngf_infoinv_trainer *t, const float *const *grad, float *const *m, f
                                (const double *)nullptr, grad ? grad[p] : (const float *)t->grads[p], t->tex[p], a);
         HIP_TRY(hipGetLastError());
     }
-    IiAdamDense D;
+    AdamDense<kIiDense> D;
     int32_t at = 0;
     for (int j = 0; j < kIiDense; ++j) {
         const int k = 3 + j;
         D.p[j] = (float *)ps[k]; D.m[j] = m[k]; D.v[j] = v[k]; D.g[j] = grad ? grad[k] : (const float *)t->grads[k];
         D.begin[j] = at;
-        D.a[j] = ii_adam_args(step_count[k] > 0 ? step_count[k] : 1, lr[k], beta1, beta2, eps, 0.0f);
+        D.a[j] = adam_args(step_count[k] > 0 ? step_count[k] : 1, lr[k], beta1, beta2, eps, 0.0f);
         if (on(k)) at += (int32_t)ns[k];
     }
     D.begin[kIiDense] = at;
+    D.skip = nullptr;
     if (at > 0) {
-        hipLaunchKernelGGL(ii_adam_dense_kernel, dim3((at + 255) / 256), dim3(256), 0, st, D);
+        hipLaunchKernelGGL(adam_dense_all_kernel<kIiDense>, dim3((at + 255) / 256), dim3(256), 0, st, D);
         HIP_TRY(hipGetLastError());
     }
     return NGF_OK;
@@ -198,14 +164,14 @@ extern "C" {
 
 int32_t ngf_sizeof_infoinv_train_desc(void) { return (int32_t)sizeof(ngf_infoinv_train_desc); }
 
-int64_t ngf_infoinv_trainer_bytes(const ngf_infoinv_trainer *t) { return t ? t->bytes : 0; }
+int64_t ngf_infoinv_trainer_bytes(const ngf_infoinv_trainer *t) { return t ? t->mem.bytes : 0; }
 
 int ngf_infoinv_trainer_destroy(ngf_infoinv_trainer *t)
 {
     if (!t) return NGF_OK;
     {
         DeviceScope ds(t->device);
-        ii_free(t);
+        t->mem.free_all();
     }
     delete t;
     return NGF_OK;
@@ -238,10 +204,10 @@ int ngf_infoinv_trainer_create(const ngf_infoinv_train_desc *desc, ngf_infoinv_t
     t->cap = cap;
     IiArgs &A = t->A;
     int rc = 0;
-    auto bail = [&](int r) { ii_free(t); delete t; return r; };
+    auto bail = [&](int r) { t->mem.free_all(); delete t; return r; };
     for (int p = 0; p < 3; ++p) {
         const int64_t tex = (int64_t)(d.plane_h[p] + 2) * (d.plane_w[p] + 2);
-        if ((rc = ii_alloc_n(t, &t->tex[p], tex * kIiC)) || (rc = ii_alloc_n(t, &t->gacc[p], tex * kIiC))) return bail(rc);
+        if ((rc = t->mem.alloc(&t->tex[p], tex * kIiC)) || (rc = t->mem.alloc(&t->gacc[p], tex * kIiC))) return bail(rc);
         Tex &x = A.tex[p];
         x.p = t->tex[p]; x.W = d.plane_w[p]; x.H = d.plane_h[p]; x.stride = d.plane_w[p] + 2;
         x.fw = (float)(d.plane_w[p] - 1); x.fh = (float)(d.plane_h[p] - 1);
@@ -249,31 +215,31 @@ int ngf_infoinv_trainer_create(const ngf_infoinv_train_desc *desc, ngf_infoinv_t
     }
     if (d.mask_bits) {
         const size_t mb = ((size_t)d.mask_d * d.mask_h * d.mask_w + 7) / 8;
-        if ((rc = ii_alloc_n(t, &t->mask, mb))) return bail(rc);
+        if ((rc = t->mem.alloc(&t->mask, mb))) return bail(rc);
         if (hipMemcpyAsync(t->mask, d.mask_bits, mb, hipMemcpyDeviceToDevice, st) != hipSuccess) return bail(fail(NGF_E_HIP, "mask copy failed"));
     }
-    if ((rc = ii_alloc_n(t, &t->dw1t, kIiDIn * kIiDH)) || (rc = ii_alloc_n(t, &t->cw1t, kIiCIn * kIiCH))) return bail(rc);
+    if ((rc = t->mem.alloc(&t->dw1t, kIiDIn * kIiDH)) || (rc = t->mem.alloc(&t->cw1t, kIiCIn * kIiCH))) return bail(rc);
     const int64_t nr = d.max_rays;
     A.cap = cap;
-    if ((rc = ii_alloc_n(t, &A.et, cap)) || (rc = ii_alloc_n(t, &A.sg, cap)) || (rc = ii_alloc_n(t, &A.w, cap)) || (rc = ii_alloc_n(t, &A.tb, cap)) ||
-        (rc = ii_alloc_n(t, &A.dxs, cap)) || (rc = ii_alloc_n(t, &A.xn, 3 * cap)) || (rc = ii_alloc_n(t, &A.valid, cap)) ||
-        (rc = ii_alloc_n(t, &A.d_in, kIiDIn * cap)) || (rc = ii_alloc_n(t, &A.d_h1, kIiDH * cap)) || (rc = ii_alloc_n(t, &A.d_h2, kIiDH * cap)) ||
-        (rc = ii_alloc_n(t, &A.d_d1, kIiDH * cap)) || (rc = ii_alloc_n(t, &A.d_d2, kIiDH * cap)) || (rc = ii_alloc_n(t, &A.d_g, kIiDIn * cap)) ||
-        (rc = ii_alloc_n(t, &A.count, nr)) || (rc = ii_alloc_n(t, &A.offset, nr + 1)) || (rc = ii_alloc_n(t, &A.list, cap)) ||
-        (rc = ii_alloc_n(t, &A.c_in, kIiCIn * cap)) || (rc = ii_alloc_n(t, &A.c_h1, kIiCH * cap)) || (rc = ii_alloc_n(t, &A.c_h2, kIiCH * cap)) ||
-        (rc = ii_alloc_n(t, &A.c_rgb, 3 * cap)) || (rc = ii_alloc_n(t, &A.c_d1, kIiCH * cap)) || (rc = ii_alloc_n(t, &A.c_d2, kIiCH * cap)) ||
-        (rc = ii_alloc_n(t, &A.c_d3, 3 * cap)) || (rc = ii_alloc_n(t, &A.c_g, kIiCF * cap)) || (rc = ii_alloc_n(t, &A.pre, 3 * nr)) ||
-        (rc = ii_alloc_n(t, &A.bound, kIiBoundBlocks + 1)) || (rc = ii_alloc_n(t, &t->m64, kIiCH * kIiCIn)))
+    if ((rc = t->mem.alloc(&A.et, cap)) || (rc = t->mem.alloc(&A.sg, cap)) || (rc = t->mem.alloc(&A.w, cap)) || (rc = t->mem.alloc(&A.tb, cap)) ||
+        (rc = t->mem.alloc(&A.dxs, cap)) || (rc = t->mem.alloc(&A.xn, 3 * cap)) || (rc = t->mem.alloc(&A.valid, cap)) ||
+        (rc = t->mem.alloc(&A.d_in, kIiDIn * cap)) || (rc = t->mem.alloc(&A.d_h1, kIiDH * cap)) || (rc = t->mem.alloc(&A.d_h2, kIiDH * cap)) ||
+        (rc = t->mem.alloc(&A.d_d1, kIiDH * cap)) || (rc = t->mem.alloc(&A.d_d2, kIiDH * cap)) || (rc = t->mem.alloc(&A.d_g, kIiDIn * cap)) ||
+        (rc = t->mem.alloc(&A.count, nr)) || (rc = t->mem.alloc(&A.offset, nr + 1)) || (rc = t->mem.alloc(&A.list, cap)) ||
+        (rc = t->mem.alloc(&A.c_in, kIiCIn * cap)) || (rc = t->mem.alloc(&A.c_h1, kIiCH * cap)) || (rc = t->mem.alloc(&A.c_h2, kIiCH * cap)) ||
+        (rc = t->mem.alloc(&A.c_rgb, 3 * cap)) || (rc = t->mem.alloc(&A.c_d1, kIiCH * cap)) || (rc = t->mem.alloc(&A.c_d2, kIiCH * cap)) ||
+        (rc = t->mem.alloc(&A.c_d3, 3 * cap)) || (rc = t->mem.alloc(&A.c_g, kIiCF * cap)) || (rc = t->mem.alloc(&A.pre, 3 * nr)) ||
+        (rc = t->mem.alloc(&A.bound, kIiBoundBlocks + 1)) || (rc = t->mem.alloc(&t->m64, kIiCH * kIiCIn)))
         return bail(rc);
     const int64_t chunks = (cap + kIiChunk - 1) / kIiChunk;
     t->part_elems = chunks * kIiCH * (kIiCIn + 1);
-    if ((rc = ii_alloc_n(t, &t->part, t->part_elems))) return bail(rc);
-    if ((rc = ii_alloc_n(t, &t->f_rgb, 3 * nr)) || (rc = ii_alloc_n(t, &t->f_depth, nr)) || (rc = ii_alloc_n(t, &t->f_drgb, 3 * nr)) ||
-        (rc = ii_alloc_n(t, &t->partb, ((cap + kIiMmChunk - 1) / kIiMmChunk) * kIiCH)))
+    if ((rc = t->mem.alloc(&t->part, t->part_elems))) return bail(rc);
+    if ((rc = t->mem.alloc(&t->f_rgb, 3 * nr)) || (rc = t->mem.alloc(&t->f_depth, nr)) || (rc = t->mem.alloc(&t->f_drgb, 3 * nr)) ||
+        (rc = t->mem.alloc(&t->partb, ((cap + kIiMmChunk - 1) / kIiMmChunk) * kIiCH)))
         return bail(rc);
     for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k) {
         t->grad_elems[k] = ns[k];
-        if ((rc = ii_alloc_n(t, &t->grads[k], ns[k]))) return bail(rc);
+        if ((rc = t->mem.alloc(&t->grads[k], ns[k]))) return bail(rc);
     }
     // the geometry of the desc
     for (int k = 0; k < 3; ++k) {

@@ -35,6 +35,7 @@
 // strides and live in LDS for the whole kernel (57-61 KB per workgroup); tiles of 16 samples live in wave-private LDS as
 // [k][16] so that a lane's MFMA B operand is in[k][sample].
 #pragma once
+#include "ngf_adam.hpp"
 #include "ngf_device.hpp"
 #include "ngf_render.hpp"
 #include "ngf_stage.hpp"          // wave_min
@@ -1894,20 +1895,7 @@ __global__ void __launch_bounds__(256) train_density_finish_kernel(const FinishA
 }
 
 // ---- 8. torch.optim.Adam (betas, eps, no weight decay, no amsgrad), float32 like the reference ------------------------------------
-struct AdamArgs {
-    float lr, beta1, beta2, eps;
-    float bc1, bc2_sqrt;       // 1 - beta1^t, sqrt(1 - beta2^t)
-    float l1;                  // planes: L1_reg_weight / numel, added as l1 * sign(p); 0 otherwise
-};
-
-__device__ __forceinline__ float adam_one(float p, float g, float &m, float &v, const AdamArgs &a)
-{
-    m = m + (1.0f - a.beta1) * (g - m);                   // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * a.beta2 + ((1.0f - a.beta2) * g) * g;         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
-    const float step = a.lr / a.bc1;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    return p - step * (m / denom);
-}
+// AdamArgs, adam_one and the dense kernel for all MLP parameters (adam_dense_all_kernel<kDenseParams>): ngf_adam.hpp
 
 // skip: device flag of the trainer (overflow[0], see train_prefix_kernel) -- non-zero: the step's gradient is incomplete, nothing is updated
 __global__ void __launch_bounds__(256) adam_dense_kernel(float *p, const float *g, float *m, float *v, int64_t n, const AdamArgs a, const int32_t *skip)
@@ -1921,30 +1909,7 @@ __global__ void __launch_bounds__(256) adam_dense_kernel(float *p, const float *
     }
 }
 
-// every MLP parameter in one launch: segment k = elements [begin[k], begin[k+1]) of the concatenation, each with its own step count / lr
-constexpr int kDenseParams = 9;
-struct AdamDenseAll {
-    float *p[kDenseParams], *m[kDenseParams], *v[kDenseParams];
-    const float *g[kDenseParams];
-    int32_t begin[kDenseParams + 1];           // begin[k+1] == begin[k] for a skipped parameter
-    AdamArgs a[kDenseParams];
-    const int32_t *skip;
-};
-
-__global__ void __launch_bounds__(256) adam_dense_all_kernel(const AdamDenseAll D)
-{
-    if (D.skip && *D.skip) return;
-    const int total = D.begin[kDenseParams];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        int k = 0;
-#pragma unroll
-        for (int j = 1; j < kDenseParams; ++j) k += (i >= D.begin[j]) ? 1 : 0;
-        const int e = i - D.begin[k];
-        float mi = D.m[k][e], vi = D.v[k][e];
-        D.p[k][e] = adam_one(D.p[k][e], D.g[k][e], mi, vi, D.a[k]);
-        D.m[k][e] = mi; D.v[k][e] = vi;
-    }
-}
+constexpr int kDenseParams = 9;             // the MLP parameters (TP_DENS_W .. TP_B3 of ngf_train.hip)
 
 // NCHW parameter [C,H,W]; gradient AND the trainer's packed copy of the parameter in the packed layouts: channels [0,CS) in ga / ta
 // (CS per texel), [CS,C) in gb / tb (C-CS per texel).  A workgroup takes 64 texels of one row: the packed gradient rows go through LDS

@@ -42,8 +42,7 @@ struct ngf_uv_trainer {
     ngf_uv_train_desc desc{};
     LayerShape shape[L];
     int64_t cap = 0;                         // max_rays * max_samples
-    std::vector<void *> allocs;
-    int64_t bytes = 0;
+    DeviceAllocs mem{0, 16};                 // every device buffer of the handle
     // per-sample buffers of the last forward (row counts: cap)
     float *seg = nullptr, *opac = nullptr, *acct = nullptr, *xraw = nullptr, *uv = nullptr;
     int32_t *cnt = nullptr, *off = nullptr, *total = nullptr, *list = nullptr, *vid = nullptr;
@@ -68,31 +67,6 @@ struct ngf_uv_trainer {
 };
 
 namespace {
-
-int uvt_alloc(ngf_uv_trainer *t, void **p, size_t bytes)
-{
-    *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    HIP_TRY(hipMalloc(p, bytes));
-    t->allocs.push_back(*p);
-    t->bytes += (int64_t)bytes;
-    return NGF_OK;
-}
-
-template <typename T>
-int uvt_alloc_n(ngf_uv_trainer *t, T **p, int64_t n)
-{
-    void *v = nullptr;
-    int rc = uvt_alloc(t, &v, (size_t)n * sizeof(T));
-    *p = (T *)v;
-    return rc;
-}
-
-void uvt_free(ngf_uv_trainer *t)
-{
-    for (void *p : t->allocs) (void)hipFree(p);
-    t->allocs.clear();
-}
 
 int launch_gemm(const UvtGemm &G, unsigned gx, unsigned gy, unsigned gz, hipStream_t st)
 {
@@ -155,14 +129,14 @@ extern "C" {
 
 int32_t ngf_sizeof_uv_train_desc(void) { return (int32_t)sizeof(ngf_uv_train_desc); }
 
-int64_t ngf_uv_trainer_bytes(const ngf_uv_trainer *t) { return t ? t->bytes : 0; }
+int64_t ngf_uv_trainer_bytes(const ngf_uv_trainer *t) { return t ? t->mem.bytes : 0; }
 
 int ngf_uv_trainer_destroy(ngf_uv_trainer *t)
 {
     if (!t) return NGF_OK;
     {
         DeviceScope ds(t->device);
-        uvt_free(t);
+        t->mem.free_all();
     }
     delete t;
     return NGF_OK;
@@ -190,8 +164,8 @@ int ngf_uv_trainer_create(const ngf_uv_train_desc *desc, ngf_uv_trainer **out, v
     const int64_t cap = d.max_rays * (int64_t)d.max_samples;
     t->cap = cap;
     int rc = NGF_OK;
-    auto F = [&](float **p, int64_t n) { if (!rc) rc = uvt_alloc_n(t, p, n); };
-    auto I = [&](int32_t **p, int64_t n) { if (!rc) rc = uvt_alloc_n(t, p, n); };
+    auto F = [&](float **p, int64_t n) { if (!rc) rc = t->mem.alloc(p, (size_t)n); };
+    auto I = [&](int32_t **p, int64_t n) { if (!rc) rc = t->mem.alloc(p, (size_t)n); };
     F(&t->seg, cap); F(&t->opac, cap); F(&t->acct, cap); F(&t->xraw, d.max_rays * 4); F(&t->uv, cap * 3);
     I(&t->cnt, d.max_rays); I(&t->off, d.max_rays); I(&t->total, 1); I(&t->list, cap); I(&t->vid, cap);
     F(&t->Xga, cap * 64); F(&t->Xg, cap * 64); F(&t->Xt, cap * 64); F(&t->X2, cap * 296);
@@ -202,7 +176,7 @@ int ngf_uv_trainer_create(const ngf_uv_train_desc *desc, ngf_uv_trainer **out, v
         t->out_ld[l] = ld;
         F(&t->out[l], cap * ld);
     }
-    if (rc) { uvt_free(t); delete t; return rc; }
+    if (rc) { t->mem.free_all(); delete t; return rc; }
     for (int l = 0; l < L; ++l) {
         if (l == 0) { t->in[l] = t->Xg; t->in_ld[l] = 64; }
         else if (l == 12) { t->in[l] = t->Xga; t->in_ld[l] = 64; }
@@ -221,7 +195,7 @@ int ngf_uv_trainer_create(const ngf_uv_train_desc *desc, ngf_uv_trainer **out, v
     }
     t->grad_elems = g;
     F(&t->grads, g);
-    if (rc) { uvt_free(t); delete t; return rc; }
+    if (rc) { t->mem.free_all(); delete t; return rc; }
     *out = t;
     return NGF_OK;
 }

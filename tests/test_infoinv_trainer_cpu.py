@@ -18,7 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "neural-gauge-fields_amd", "csrc")
 NEW = ["ngf_infoinv_train_step_backward", "ngf_infoinv_train_set_moments", "ngf_infoinv_train_adam_all", "ngf_infoinv_train_get_grad",
        "ngf_infoinv_train_adam_ext"]
-NEW_KERNELS = ["ii_loss_kernel", "ii_mm_kernel", "ii_mm_reduce_kernel", "ii_plane_grad_add_kernel", "ii_adam_plane_kernel", "ii_adam_dense_kernel"]
+NEW_KERNELS = ["ii_loss_kernel", "ii_mm_kernel", "ii_mm_reduce_kernel", "ii_plane_grad_add_kernel", "ii_adam_plane_kernel",
+               "adam_dense_all_kernelILi13E"]          # the shared dense kernel (csrc/ngf_adam.hpp) at the thirteen decoder tensors
 
 
 def test_fused_trainer_symbols_are_exported_by_both_libraries_at_abi_5():

@@ -3,7 +3,8 @@ positional-factor chain (v_pk_mov_b32, crossed-halves v_pk_mul_f32 / negated v_p
 operations as single VALU instructions are bit-stable.  The mechanism below the ISA is unknown, so the instruction FORMS that only the unstable
 build contains (profiles/r04_isa_packed_diff.txt) are forbidden mechanically in every kernel that issues bf16 matrix instructions:
 profiles/isa_hazards.py --lint on the assembly of the shipped translation units -- and, so that the fence is known to catch what it is for, on
-the -DNGF_EXP_PACKED_PE build, which must be flagged.  Compiles three translation units with -save-temps (hipcc cross-compiles without a GPU)."""
+the -DNGF_EXP_PACKED_PE build, which must be flagged.  Compiles the field, TriPlane trainer and UV-Mapping translation units with -save-temps (hipcc
+cross-compiles without a GPU)."""
 import os
 import subprocess
 import sys
@@ -22,7 +23,7 @@ def asm(tmp_path_factory):
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not found")
     jobs = {}
-    for tag, src, defs in (("field", "ngf_field.hip", []), ("uv", "ngf_uv.hip", []), ("field_packed", "ngf_field.hip", ["-DNGF_EXP_PACKED_PE=1"]),
+    for tag, src, defs in (("field", "ngf_field.hip", []), ("train", "ngf_train.hip", []), ("uv", "ngf_uv.hip", []), ("field_packed", "ngf_field.hip", ["-DNGF_EXP_PACKED_PE=1"]),
                            ("uv_short_nops", "ngf_uv.hip", ["-DNGF_EXP_UV_SHORT_NOPS=1"])):
         d = tmp_path_factory.mktemp(tag)
         jobs[tag] = (d, src, subprocess.Popen([hipcc] + FLAGS + defs + [os.path.join(CSRC, src), "-o", "out.o"], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
@@ -66,6 +67,7 @@ def test_shipped_hot_kernels_use_no_scratch(asm):
     the ray loop and spilled) and for the production render kernels of the default levels; held here so a source change that brings spills back fails
     on the CPU."""
     scratch = {**_kernel_blocks(asm["uv"]), **_kernel_blocks(asm["field"])}
+    train = _kernel_blocks(asm["train"])
     want = ["uv_render_kernelILi2ELb0", "uv_render_kernelILi2ELb1", "uv_render_kernelILi1ELb0",
             "render_kernelINS_14TriPlanePolicyILb1ELb1ELi12ELi1ELb0EEELb1ELb0E",      # level 3 (module default), production instantiation
             "render_kernelINS_14TriPlanePolicyILb1ELb0ELi12ELi1ELb0EEELb1ELb0E",      # level 2
@@ -74,14 +76,15 @@ def test_shipped_hot_kernels_use_no_scratch(asm):
             "render_kernelINS_8MaskSkipINS_23TriPlaneBakedBf16PolicyEEELb1ELb0E",                     # level 3 + bf16 layer 2, the same
             "render_kernelINS_8MaskSkipINS_14InfoInvPolicyTILb1ELb0EEEEELb1ELb0E",                    # InfoInv split bf16, the same (the fp32 one carries 52 B there: profiles/r06_mask_skip.txt)
             "render_kernelINS_14InfoInvPolicyTILb0ELb0EEELb1ELb0E",                   # InfoInv fp32
-            "render_kernelINS_14InfoInvPolicyTILb1ELb0EEELb1ELb0E",                   # InfoInv split bf16
+            "render_kernelINS_14InfoInvPolicyTILb1ELb0EEELb1ELb0E"]                   # InfoInv split bf16
+    want_train = [
             # round 6: the kernels of a training step -- train_density_bwd_kernel<true, true> carried 28 B per lane through round 5
             # (its two profiling counters lived in an array behind a maybe-null pointer)
             "train_density_kernel", "train_scan_kernel", "train_color_fwd16_kernel", "train_composite_bwd_kernel", "train_color_bwd_kernel",
             "train_bin_scatter_kernel", "train_bin_gather_kernel", "xty_all_kernel", "train_density_bwd_kernel", "train_density_finish_kernel",
             "adam_plane_kernel", "adam_dense_all_kernel"]
-    for needle in want:
-        hits = {k: v for k, v in scratch.items() if needle in k}
+    for needle, unit in [(n, scratch) for n in want] + [(n, train) for n in want_train]:          # the trainer's kernels: in the trainer's translation unit
+        hits = {k: v for k, v in unit.items() if needle in k}
         assert hits, f"no kernel matches {needle}"
         assert all(v == 0 for v in hits.values()), hits
 
@@ -179,6 +182,7 @@ def test_matrix_results_stored_to_lds_from_agprs_wait_long_enough(asm):
     assert checked_short == checked and bad_short, "the lint does not see the shortened wait states"
     # no other translation unit stores from AGPRs by hand
     assert isa_hazards.lint_mfma_to_lds(asm["field"])[1] == 0
+    assert isa_hazards.lint_mfma_to_lds(asm["train"])[1] == 0
 
 
 def test_dpp_reads_keep_two_wait_states_behind_valu_writes(asm):
@@ -186,9 +190,12 @@ def test_dpp_reads_keep_two_wait_states_behind_valu_writes(asm):
     split_chain, split_chain_rows; the trainer's scan): a VALU write of a VGPR followed by a DPP read of it needs 2 wait states.  Held on the
     shipped assembly -- and shown to bite on a synthetic kernel."""
     import isa_hazards
-    bad, checked = isa_hazards.lint_valu_to_dpp(asm["field"])
+    checked = 0
+    for tag in ("field", "train"):
+        bad, n = isa_hazards.lint_valu_to_dpp(asm[tag])
+        assert not bad, (tag, bad[:5])
+        checked += n
     assert checked > 5000, checked
-    assert not bad, bad[:5]
     import tempfile
     snippet = "_Zfake:\n\tv_add_f32_e32 v1, v2, v3\n\ts_nop 0\n\tv_add_f32_dpp v4, v1, v1 row_shr:1 row_mask:0xf bank_mask:0xf\n\ts_endpgm\n"
     ok = snippet.replace("s_nop 0", "s_nop 1")
