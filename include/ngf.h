@@ -457,7 +457,10 @@ int ngf_uv_render_batch(const ngf_uv *m, const float *campos_dev, const float *r
  * they are packed), "grid" (upper bound of the workgroups of a render launch: with 1 every wave of the only workgroup takes many tiles
  * one after the other), "xcd" (1: one tile queue per XCD with stealing; default 0: a single queue -- measured neutral on the
  * SIMD-bound frames, profiles/r03_xcd_queues.txt).  The knobs are independent atomics: setting one while another thread launches is safe, but a launch sees
- * whatever values are current when it reads them -- they are test / experiment switches, not a per-call API. */
+ * whatever values are current when it reads them -- they are test / experiment switches, not a per-call API.
+ * "waves" at level 3 (NGF_F_BAKE_DENSITY | NGF_F_BAKE_COLOR): 16 = the sixteen-wave kernel (four waves per SIMD), 12 = the twelve-wave one; a field
+ * whose MLP image leaves no room for sixteen waves in the CU's LDS keeps twelve.  ngf_debug_get("last_waves") (read only) = the waves per
+ * workgroup of the last render launch. */
 int ngf_debug_set(const char *name, int32_t value);
 int32_t ngf_debug_get(const char *name);
 /* the "poison" bit-0 launch on its own: fill the LDS of every CU with 0x7FC0DEAD on `hip_stream` (tests) */

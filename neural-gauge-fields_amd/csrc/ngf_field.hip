@@ -37,6 +37,7 @@ static const char *const g_knob_name[ngf::KNOB_COUNT] = {"tile_w", "split", "wav
 static bool g_knob_init = [] { for (auto &k : g_knob) k.store(-1); return true; }();
 
 int ngf::knob(int id) { return g_knob[id].load(std::memory_order_relaxed); }
+static std::atomic<int> g_last_waves{-1};      // waves per workgroup of the last render launch (ngf_debug_get("last_waves"): the tests see which kernel a launch took)
 
 hipError_t ngf::ensure_dynamic_lds(const void *kernel, size_t bytes)
 {
@@ -128,6 +129,7 @@ extern "C" int32_t ngf_debug_get(const char *name)
     if (name)
         for (int k = 0; k < ngf::KNOB_COUNT; ++k)
             if (!strcmp(name, g_knob_name[k])) return g_knob[k].load();
+    if (name && !strcmp(name, "last_waves")) return g_last_waves.load();      // read-only
     return -1;
 }
 
@@ -1139,6 +1141,7 @@ static int launch_render(K kernel, K kernel_split, K kernel_prod, const ngf_fiel
     A.queue_waves = (uint32_t)grid;          // one report per workgroup (queue_done)
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(threads), lds_bytes, st, A);
     HIP_TRY(hipGetLastError());
+    g_last_waves.store(waves, std::memory_order_relaxed);
     return NGF_OK;
 }
 
@@ -1187,17 +1190,49 @@ static int launch_pc(const ngf_field *f, RenderArgs &A, hipStream_t st)
 }
 #endif
 
+// Level 3 at sixteen waves per CU (TriPlanePolicy::W16: four waves per SIMD, 1024-thread workgroups, the pass in 128 registers; DESIGN.md section
+// 4.1, profiles/r09_waves16.txt: the 640 000-ray frame 4.239 -> 4.000 ms).  Which kernel a level-3 launch takes is decided here, per launch, like
+// gauge_same:
+//   - knob waves = 16 / 12 asks for one of them (the tests and the scripts under profiles/ compare the two in one process);
+//   - otherwise sixteen waves from kW16MinRaysPerCu rays per CU on.  A short launch is one narrow tile per wave, and four such waves on a SIMD
+//     share its matrix pipe where three did: 4 096 rays 0.107 -> 0.129 ms, 20 000 rays 0.239 -> 0.253 ms, 40 000 rays 0.351 -> 0.362 ms with
+//     sixteen waves; 80 000 rays (one rank's shard of an eight-GPU frame) 0.605 -> 0.602 ms, 160 000 rays 1.116 -> 1.075 ms;
+//   - a field whose MLP image does not leave room for sixteen waves' queues and view tables in the CU's 160 KiB keeps the twelve-wave kernel
+//     whatever was asked for -- never an error.  (The level-3 image is 21.3 KiB for every preset -- the baked planes have 64 channels whatever the
+//     appearance width -- so today every level-3 field fits: 21.3 + 16 x 8.25 = 153.3 KiB.)
+static constexpr int64_t kW16MinRaysPerCu = 312;      // 80 000 rays on 256 CUs: the smallest launch measured at which sixteen waves do not lose
+static bool level3_waves16(const ngf_field *f, const RenderArgs &A)
+{
+    using P = TriPlanePolicy<true, true, 16, 1>;
+    static_assert(P::W16 && P::PROD && P::REC12 && P::VLDS && P::VIEW_FOLD, "the sixteen-wave level-3 policy is the production pass");
+    const size_t lds = ((size_t)((A.blob_floats + 3) & ~3) + P::WAVES * wave_lds_floats<P>()) * sizeof(float);
+    if (lds > 160 * 1024) return false;
+    if (knob(KNOB_WAVES) >= 0) return knob(KNOB_WAVES) == 16;
+    return A.n >= kW16MinRaysPerCu * f->num_cus;
+}
+
+// the fused kernel at W waves per CU; a field with an alpha mask takes the instantiation whose march skips empty space (levels 2 and 3)
+template <bool BD, bool BC, int W>
+static int launch_fused(const ngf_field *f, RenderArgs &A, hipStream_t st)
+{
+    if constexpr (BD) {
+        if (A.mask.coarse) return launch_policy<MaskSkip<TriPlanePolicy<BD, BC, W, 1>>>(f, A, st);
+    }
+    return launch_policy<TriPlanePolicy<BD, BC, W, 1>>(f, A, st);
+}
+
 template <bool BD, bool BC>
 static int launch_triplane(const ngf_field *f, RenderArgs &A, hipStream_t st)
 {
 #ifndef NGF_EXPERIMENTS
-    // product library: the fused kernel, twelve waves per CU, one march step per lane (measured best, profiles/r01_sweep.txt)
-    if (knob(KNOB_KERNEL) > 0 || knob(KNOB_STAGE) > 0 || knob(KNOB_PROFILE) > 0 || knob(KNOB_NSTEP) > 1 || (knob(KNOB_WAVES) >= 0 && knob(KNOB_WAVES) != 12))
+    // product library: the fused kernel, one march step per lane, twelve waves per CU (measured best, profiles/r01_sweep.txt) -- level 3: see level3_waves16
+    if (knob(KNOB_KERNEL) > 0 || knob(KNOB_STAGE) > 0 || knob(KNOB_PROFILE) > 0 || knob(KNOB_NSTEP) > 1 ||
+        (knob(KNOB_WAVES) >= 0 && knob(KNOB_WAVES) != 12 && !(BD && BC && knob(KNOB_WAVES) == 16)))
         return fail(NGF_E_UNSUPPORTED, "knobs kernel / stage / profile / nstep / waves select experiment kernels: load libngf_hip_exp.so (built with -DNGF_EXPERIMENTS)");
-    if constexpr (BD) {
-        if (A.mask.coarse) return launch_policy<MaskSkip<TriPlanePolicy<BD, BC, 12, 1>>>(f, A, st);      // a field with an alpha mask: the march skips empty space (levels 2 and 3)
+    if constexpr (BD && BC) {
+        if (level3_waves16(f, A)) return launch_fused<BD, BC, 16>(f, A, st);
     }
-    return launch_policy<TriPlanePolicy<BD, BC, 12, 1>>(f, A, st);
+    return launch_fused<BD, BC, 12>(f, A, st);
 #else
     // default: the fused kernel (every wave marches and shades).  ngf_debug_set("kernel", 1) selects the specialised march / shade
     // waves of ngf_render_pc.hpp: bit-identical, but SLOWER on gfx950 (R1 frame 10.7-12.7 ms vs 10.0 ms, profiles/r02_pc_kernel.txt),
@@ -1243,13 +1278,12 @@ static int launch_triplane(const ngf_field *f, RenderArgs &A, hipStream_t st)
     if (knob(KNOB_PROFILE) > 0) {      // stats[4..9] += section cycles (profiles/exp_sections.py); stats must hold 10 counters
         if constexpr (!BC) return launch_policy<TriPlanePolicy<BD, false, 12, 1, true>>(f, A, st);
     }
+    if constexpr (BD && BC) {      // level 3: waves = 16 is the 128-register production pass, waves = 12 the twelve-wave one, no knob the product library's choice
+        if (w == 12 || w == 16) return level3_waves16(f, A) ? launch_fused<BD, BC, 16>(f, A, st) : launch_fused<BD, BC, 12>(f, A, st);
+    }
     switch (w) {
     case 8: return launch_policy<TriPlanePolicy<BD, BC, 8, 1>>(f, A, st);
-    case 12:
-        if constexpr (BD) {
-            if (A.mask.coarse) return launch_policy<MaskSkip<TriPlanePolicy<BD, BC, 12, 1>>>(f, A, st);
-        }
-        return launch_policy<TriPlanePolicy<BD, BC, 12, 1>>(f, A, st);
+    case 12: return launch_fused<BD, BC, 12>(f, A, st);
     case 16: return launch_policy<TriPlanePolicy<BD, BC, 16, 1>>(f, A, st);
     default: return fail(NGF_E_ARG, "knob waves must be 8, 12 or 16");
     }

@@ -231,7 +231,11 @@ __device__ __forceinline__ void triplane_gauge(const RenderArgs &A, const float 
 template <bool BAKE_D, bool BAKE_C, int WAVES_, int NSTEP_, bool PROFILE_ = false>
 struct TriPlanePolicy {
     static constexpr bool PROFILE = PROFILE_;
-    static constexpr bool PROD = WAVES_ == 12 && NSTEP_ == 1 && !PROFILE_;      // has a production (DBG = false) instantiation of the split kernel
+    // W16: the sixteen-wave level-3 policy (four waves per SIMD, 128 registers per lane): the twelve-wave pass -- view inputs in LDS, per-ray view
+    // fold, 12-float records -- with the colour gather in quarter-plane stages (ngf_shade16.hpp baked16_layer1_quarters).  The other sixteen-wave
+    // policies (levels 0-2, experiment library) stay the round-1 tuning variants.
+    static constexpr bool W16 = WAVES_ == 16 && BAKE_D && BAKE_C && NSTEP_ == 1 && !PROFILE_;
+    static constexpr bool PROD = (WAVES_ == 12 || W16) && NSTEP_ == 1 && !PROFILE_;      // has a production (DBG = false) instantiation of the split kernel
     static constexpr bool INFOINV = false;
     static constexpr bool MASK_SKIP = false;                    // empty-space skipping through the mask's block image (march loop): MaskSkip<P> below
     static constexpr bool STAGED = false;                       // ngf_stage.hpp: LDS-staged texture strips
@@ -239,13 +243,13 @@ struct TriPlanePolicy {
     static constexpr int WAVES = WAVES_;
     static constexpr int NSTEP = NSTEP_;
     static constexpr int BATCH = kBatch16;
-    static constexpr bool VLDS = WAVES_ <= 12;                  // per-ray view inputs cached in LDS (4 KB / wave) or recomputed per pass
+    static constexpr bool VLDS = WAVES_ <= 12 || W16;           // per-ray view inputs cached in LDS (4 KB / wave) or recomputed per pass
     static constexpr int VFEAT_FLOATS = VLDS ? kWave * kViewFeat : 0;       // view inputs of up to 64 rays (+ the per-ray fold table of small tiles)
     static constexpr int RING = NSTEP_ == 1 ? 128 : 256;        // >= BATCH-1 + 64*NSTEP records
     // REC12 (split kernel of the default twelve-wave policies): a queue record carries the sample's three bilinear cells (texel index, fractional
     // parts, in-range bit) instead of its six coordinates, so a shade pass starts its gathers at once and spends 8 instead of ~28 instructions per
     // plane on the cell -- all 64 lanes of a pass used to redo the three setups of their 16 samples that the march had already done.
-    static constexpr bool REC12 = WAVES_ == 12 && NSTEP_ == 1 && !PROFILE_;
+    static constexpr bool REC12 = (WAVES_ == 12 || W16) && NSTEP_ == 1 && !PROFILE_;
     static constexpr bool GATHER_QUAD = BAKE_C;                 // the shade's gather lane 4 s + kq works for sample lane >> 2 (ngf_shade16.hpp mlp_pass16_baked): shade12 takes ITS cells
     static constexpr bool SHARED_GAUGE = BAKE_D;                 // sigma() takes the shared-axis gauge set-up: launched only for RenderArgs::gauge_same, GaugeAny<P> otherwise
     template <bool SAME>
@@ -295,7 +299,7 @@ struct TriPlanePolicy {
     {
         f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
         if (!pre) v = VLDS ? *reinterpret_cast<const f32x4 *>(vf + (lane >> 4) * 4) : view_entries16(od, lane >> 4);
-        if constexpr (BAKE_C) mlp_pass16_baked(A, smem, rec, v, lane, c, pre);
+        if constexpr (BAKE_C) mlp_pass16_baked<W16>(A, smem, rec, v, lane, c, pre);
         else mlp_pass16<48>(A, smem, rec, v, lane, c, tk, pre);
     }
     // REC12 form: the cells come from the record
@@ -305,7 +309,7 @@ struct TriPlanePolicy {
         const float rec[kRecFloats] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
         if (!pre) v = *reinterpret_cast<const f32x4 *>(vf + (lane >> 4) * 4);
-        if constexpr (BAKE_C) mlp_pass16_baked(A, smem, rec, v, lane, c, pre, &cells);
+        if constexpr (BAKE_C) mlp_pass16_baked<W16>(A, smem, rec, v, lane, c, pre, &cells);
         else mlp_pass16<48>(A, smem, rec, v, lane, c, nullptr, pre, &cells);
     }
 };

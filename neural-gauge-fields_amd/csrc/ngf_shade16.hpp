@@ -11,6 +11,9 @@
 // As in the 32-wide form the product is evaluated transposed (rows = hidden units, columns = samples): the four
 // accumulator tiles of a lane are hidden units n = mt*16 + 4*kq + r of ITS sample and feed layer 2 in place.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "ngf_device.hpp"
 
 namespace ngf {
@@ -555,13 +558,136 @@ __device__ __forceinline__ void baked16_layer1(const RenderArgs &A, const float 
     }
 }
 
+#ifndef NGF_W16_STAGES
+#define NGF_W16_STAGES 2      // quarter-plane stages in flight in the sixteen-wave pass (2 or 3)
+#endif
+
+// ---- the same front part in QUARTER-plane stages (the sixteen-wave level-3 pass: 128 registers per lane) --------------------------------
+// A stage is 4 taps x 1 float4 = ONE accumulator tile of one plane: 16 registers instead of a half plane's 32, twelve stages instead of six, NB of
+// them in flight.  What a lane loads (the quad-coalesced order: four lanes, one 64-byte line), the four FMAs per channel (tap 0, 1, 2, 3 onto the
+// running sum, planes in order) and the sixteen lane permutations are those of baked16_layer1: the sums are its bits.  A plane's texel index is
+// taken from the record when its first stage is issued, its four weights are made when its first stage is consumed (bil_from_rec_pk, the
+// operations of the half-plane form) and live for that plane's four stages only.
+struct BakedQuarter { f32x4 raw[4]; };
+
+// the cell of plane P: from the queue record's cells, or (the kernels without 12-float records) from the sample's coordinates
+__device__ __forceinline__ BilPk baked16_cell(const float rec[kRecFloats], int P, const Tex &t, const RecCells *cells)
+{
+    if (cells) return bil_from_rec_pk(cells->idx[P], cells->wx1[P], cells->wy1[P], (cells->bits >> (8 + P)) & 1);
+    const Bil b = bil_setup(rec[2 + 2 * P], rec[3 + 2 * P], t);
+    BilPk bp;
+    bp.idx = b.idx; bp.wa = f32x2{b.w00, b.w10}; bp.wb = f32x2{b.w01, b.w11};
+    return bp;
+}
+
+__device__ __forceinline__ void baked16q_issue(const float rec[kRecFloats], int st, int kq, BakedQuarter &g, const RecCells *cells)
+{
+    const int P = st >> 2, mt = st & 3;
+    const Tex t = karg_tex(offsetof(RenderArgs, app) + P * sizeof(Tex));
+    const int32_t idx = cells ? cells->idx[P] : baked16_cell(rec, P, t, cells).idx;
+    const f32x4 *t00 = tex_at<f32x4>(t.p, (uint32_t)idx * 64u + 4u * (kq + 4 * mt));
+    const f32x4 *t01 = tex_at<f32x4>(t.p, (uint32_t)(idx + t.stride) * 64u + 4u * (kq + 4 * mt));
+    g.raw[0] = t00[0];
+    g.raw[1] = t00[16];
+    g.raw[2] = t01[0];
+    g.raw[3] = t01[16];
+}
+
+__device__ __forceinline__ void baked16q_consume(const float rec[kRecFloats], int st, const BakedQuarter &g, f32x2 &wa, f32x2 &wb, f32x2 sum[8],
+                                                 const RecCells *cells)
+{
+    const int P = st >> 2, mt = st & 3;
+    if (mt == 0) {
+        const BilPk bp = baked16_cell(rec, P, cells ? Tex{} : karg_tex(offsetof(RenderArgs, app) + P * sizeof(Tex)), cells);
+        wa = bp.wa; wb = bp.wb;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int k = mt * 4 + e;
+        const float s0 = P == 0 ? 0.0f : sum[k >> 1][k & 1];
+        sum[k >> 1][k & 1] = fmaf(wb[1], g.raw[3][e], fmaf(wb[0], g.raw[2][e], fmaf(wa[1], g.raw[1][e], fmaf(wa[0], g.raw[0][e], s0))));
+    }
+}
+
+// stage ST of the twelve: accumulate it, then issue stage ST + NB into the buffer it leaves (named buffers picked at compile time: an array of them
+// indexed by the stage went to scratch)
+template <int NB, int ST>
+__device__ __forceinline__ BakedQuarter &baked16q_buffer(BakedQuarter &g0, BakedQuarter &g1, BakedQuarter &g2)
+{
+    if constexpr (ST % NB == 0) return g0;
+    else if constexpr (ST % NB == 1) return g1;
+    else return g2;
+}
+template <int NB, int... ST>
+__device__ __forceinline__ void baked16q_stages(const float rg[kRecFloats], int kqg, BakedQuarter &g0, BakedQuarter &g1, BakedQuarter &g2, f32x2 sum[8],
+                                                const RecCells *gcells, std::integer_sequence<int, ST...>)
+{
+    f32x2 wa = {0.0f, 0.0f}, wb = {0.0f, 0.0f};
+    auto stage = [&](auto st_) {
+        constexpr int st = decltype(st_)::value;
+        BakedQuarter &g = baked16q_buffer<NB, st>(g0, g1, g2);
+        baked16q_consume(rg, st, g, wa, wb, sum, gcells);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (st + NB < 12) {
+            baked16q_issue(rg, st + NB, kqg, g, gcells);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    (stage(std::integral_constant<int, ST>{}), ...);
+}
+
+template <typename L, int NB = 2>
+__device__ __forceinline__ void baked16_layer1_quarters(const RenderArgs &A, const float *blob, const float rec[kRecFloats], const f32x4 v,
+                                                        int lane, f32x4 acc[4], const float *pre, const RecCells *gcells)
+{
+    static_assert(NB == 2 || NB == 3, "two or three quarter-plane stages in flight");
+    const int kq = lane >> 4;
+    const int sg = lane >> 2, kqg = lane & 3;
+    float rg[kRecFloats];
+    rg[0] = rec[0]; rg[1] = rec[1];
+    if (!gcells) {
+#pragma unroll
+        for (int k = 2; k < kRecFloats; ++k) rg[k] = __shfl(rec[k], sg);
+    } else {
+#pragma unroll
+        for (int k = 2; k < kRecFloats; ++k) rg[k] = 0.0f;
+    }
+    BakedQuarter g0, g1, g2;
+    baked16q_issue(rg, 0, kqg, g0, gcells);
+    __builtin_amdgcn_sched_barrier(0);
+    baked16q_issue(rg, 1, kqg, g1, gcells);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (NB == 3) {
+        baked16q_issue(rg, 2, kqg, g2, gcells);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    f32x2 sum[8];
+    baked16q_stages<NB>(rg, kqg, g0, g1, g2, sum, gcells, std::make_integer_sequence<int, 12>{});
+    const int src = 4 * (lane & 15) + kq;
+    const float *b0 = pre ? pre + kq * 16 : blob + L::B1 + kq * 16;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[mt][e] = b0[4 * mt + e] + __shfl(sum[(4 * mt + e) >> 1][e & 1], src);
+    if (!pre) {
+        const float *w1 = blob + L::W1V + lane;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) acc[mt] = NGF_MFMA16(w1[(mt * 4 + j) * 64], v[j], acc[mt]);
+    }
+}
+
+// QUARTER: the sixteen-wave policy's front part (quarter-plane stages); every other kernel keeps the half-plane form and its instruction stream
+template <bool QUARTER = false>
 __device__ __forceinline__ void mlp_pass16_baked(const RenderArgs &A, const float *blob, const float rec[kRecFloats], const f32x4 v,
                                                  int lane, float rgb[3], const float *pre = nullptr, const RecCells *gcells = nullptr)
 {
     using L = MlpLayout16Baked;
     blob = per_pass16(blob);
     f32x4 acc[4];
-    baked16_layer1<L>(A, blob, rec, v, lane, acc, pre, gcells);
+    if constexpr (QUARTER) baked16_layer1_quarters<L, NGF_W16_STAGES>(A, blob, rec, v, lane, acc, pre, gcells);
+    else baked16_layer1<L>(A, blob, rec, v, lane, acc, pre, gcells);
     mlp_tail16(blob, L::W2, L::B2, L::W3, L::B3, lane, acc, rgb);
 }
 
