@@ -8,6 +8,7 @@
 
 #include "ngf_host.hpp"
 #include "ngf_infoinv.hpp"
+#include "ngf_mlp_image.hpp"
 #include "ngf_pack.hpp"
 #include "ngf_render.hpp"
 #include "ngf_alpha.hpp"
@@ -320,288 +321,6 @@ __global__ void generate_rays_dtu_kernel(int W, float fx, float fy, float cx, fl
     }
 }
 
-// ---- MLP images ------------------------------------------------------------------------------------
-// LDS images of rgb_decoder: basis (no bias, no activation; networks.py:17,26) is pre-composed with layer 1 in fp64,
-// W1' = W1[:, :F] @ basis; row / column permutations put every MFMA operand at [k-step][lane].
-// 16-wide (v_mfma_f32_16x16x4_f32) image of rgb_decoder for TriPlane (ngf_shade16.hpp).  Lane (s, kq): hidden
-// unit of accumulator (mt, r) is n = mt*16 + 4*kq + r.  With bake = true the plane part of layer 1 goes to the
-// texture baker instead: wp[p][n][c] = W1'[n][p*APPc + c] (natural unit order: channel n of a baked texel = unit n).
-// NGF_F_SPLIT_BF16: bf16 round-to-nearest-even and the 3-term split of a weight
-static uint16_t f2bf(float x)
-{
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-static float bf2f(uint16_t h)
-{
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-static void split3(float x, uint16_t out[3])
-{
-    out[0] = f2bf(x);
-    const float r1 = x - bf2f(out[0]);
-    out[1] = f2bf(r1);
-    const float r2 = r1 - bf2f(out[1]);
-    out[2] = f2bf(r2);
-}
-
-// LDS image of ngf_shade_bf16.hpp: A fragments [mt][k-block][part][lane][8 bf16]; lane (i, kq), element e of k-block kb holds the
-// weight of output unit mt*16 + i for the (kb*8 + e)-th input that lane quarter kq supplies
-static void build_rgb_image_bf16(int F, const std::vector<float> &w1p, const std::vector<float> &w1, const std::vector<float> &b1,
-                                 const std::vector<float> &w2, const std::vector<float> &b2, const std::vector<float> &w3, const std::vector<float> &b3,
-                                 float *img)
-{
-    using L = MlpLayoutBf16;
-    const int IN = F + 15, APPc = F / 3;
-    std::vector<double> w1f((size_t)64 * (F + 16), 0.0);       // W1' = [W1[:, :F] . basis | W1[:, F:F+15] | 0]
-    for (int n = 0; n < 64; ++n) {
-        for (int k = 0; k < F; ++k) w1f[(size_t)n * (F + 16) + k] = (double)w1p[(size_t)n * F + k];      // W1[:, :F] . basis, folded on the device (fold_w1_basis_kernel)
-        for (int k = 0; k < 15; ++k) w1f[(size_t)n * (F + 16) + F + k] = w1[(size_t)n * IN + F + k];
-    }
-    auto hidden = [](int mt, int r, int kq) { return mt * 16 + 4 * kq + r; };
-    uint16_t *h16 = reinterpret_cast<uint16_t *>(img);
-    auto put = [&](int base_floats, int nkb, int mt, int kb, int l, int e, float wv) {
-        uint16_t p3[3];
-        split3(wv, p3);
-        for (int part = 0; part < 3; ++part)
-            h16[((size_t)base_floats + ((((size_t)mt * nkb + kb) * 3 + part) * 64 + l) * 4) * 2 + e] = p3[part];
-    };
-    for (int mt = 0; mt < 4; ++mt)
-        for (int kb = 0; kb < L::KB1; ++kb)
-            for (int l = 0; l < 64; ++l)
-                for (int e = 0; e < 8; ++e) {
-                    const int kq = l >> 4, n = mt * 16 + (l & 15), j = kb * 8 + e;
-                    int col;
-                    if (j < 36) { const int P = j / 12, jj = j % 12; col = P * APPc + 16 * (jj / 4) + 4 * kq + (jj & 3); }
-                    else col = F + kq * 4 + (j - 36);                                   // view entry (entry 15 = zero pad column)
-                    put(L::W1, L::KB1, mt, kb, l, e, (float)w1f[(size_t)n * (F + 16) + col]);
-                }
-    for (int mt = 0; mt < 4; ++mt)
-        for (int kb = 0; kb < L::KB2; ++kb)
-            for (int l = 0; l < 64; ++l)
-                for (int e = 0; e < 8; ++e) {
-                    const int kq = l >> 4, n = mt * 16 + (l & 15), j = kb * 8 + e;
-                    put(L::W2, L::KB2, mt, kb, l, e, w2[(size_t)n * 64 + hidden(j >> 2, j & 3, kq)]);
-                }
-    for (int kq = 0; kq < 4; ++kq)
-        for (int k = 0; k < 16; ++k) {
-            const int n = hidden(k >> 2, k & 3, kq);
-            img[L::B1 + kq * 16 + k] = b1[n];
-            img[L::B2 + kq * 16 + k] = b2[n];
-            for (int c = 0; c < 3; ++c) img[L::W3 + c * 64 + kq * 16 + k] = w3[(size_t)c * 64 + n];
-        }
-    for (int c = 0; c < 3; ++c) img[L::B3 + c] = b3[c];
-    img[L::B3 + 3] = 0.0f;
-}
-
-// NGF_F_BAKE_COLOR | NGF_F_SPLIT_BF16: the level-3 image (built by build_rgb_image16 with bake = true) with its fp32 layer-2 matrix replaced by the
-// bf16 A fragments of build_rgb_image_bf16's layer 2 (MlpLayout16BakedBf16: the view k-steps stay where they are, the fp32 tables move behind)
-static void rebuild_baked_image_bf16(const std::vector<float> &baked, const std::vector<float> &w2, float *img)
-{
-    using LS = MlpLayout16Baked;
-    using LD = MlpLayout16BakedBf16;
-    memcpy(img + LD::W1V, baked.data() + LS::W1V, sizeof(float) * 4 * 4 * 64);
-    memcpy(img + LD::B1, baked.data() + LS::B1, sizeof(float) * 64);
-    memcpy(img + LD::B2, baked.data() + LS::B2, sizeof(float) * 64);
-    memcpy(img + LD::W3, baked.data() + LS::W3, sizeof(float) * 192);
-    memcpy(img + LD::B3, baked.data() + LS::B3, sizeof(float) * 4);
-    auto hidden = [](int mt, int r, int kq) { return mt * 16 + 4 * kq + r; };
-    uint16_t *h16 = reinterpret_cast<uint16_t *>(img);
-    for (int mt = 0; mt < 4; ++mt)
-        for (int kb = 0; kb < 2; ++kb)
-            for (int l = 0; l < 64; ++l)
-                for (int e = 0; e < 8; ++e) {
-                    const int kq = l >> 4, n = mt * 16 + (l & 15), j = kb * 8 + e;
-                    uint16_t p3[3];
-                    split3(w2[(size_t)n * 64 + hidden(j >> 2, j & 3, kq)], p3);
-                    for (int part = 0; part < 3; ++part)
-                        h16[((size_t)LD::W2 + ((((size_t)mt * 2 + kb) * 3 + part) * 64 + l) * 4) * 2 + e] = p3[part];
-                }
-}
-
-// NGF_F_SPLIT_BF16 for InfoInv (ngf_infoinv.hpp mlp_pass16_bf16_ii): A fragments as in build_rgb_image_bf16 -- lane (i, kq), element e of
-// k-block kb holds the weight of unit mt*16 + i for the lane quarter's (8 kb + e)-th input: 18 channels of each plane in the PACKED
-// channel order (infoinv_split_channel), its 4 view entries, 6 zero pads.  Layer 1: hi / mid parts in the LDS image
-// [mt][kb][2][lane][8 bf16], lo parts in the streamed image [kb][mt][lane][8 bf16]; layer 2: [mt][kb][3][lane][8 bf16].
-static void build_rgb_image_bf16_ii(int F, const std::vector<float> &w1p, const std::vector<float> &w1, const std::vector<float> &b1,
-                                    const std::vector<float> &w2, const std::vector<float> &b2, const std::vector<float> &w3, const std::vector<float> &b3,
-                                    float *img, std::vector<float> &lopack)
-{
-    using L = MlpLayoutBf16II;
-    const int IN = F + 15, APPc = F / 3;
-    std::vector<double> w1f((size_t)64 * (F + 16), 0.0);       // W1' = [W1[:, :F] . basis | W1[:, F:F+15] | 0]
-    for (int n = 0; n < 64; ++n) {
-        for (int k = 0; k < F; ++k) w1f[(size_t)n * (F + 16) + k] = (double)w1p[(size_t)n * F + k];      // W1[:, :F] . basis, folded on the device (fold_w1_basis_kernel)
-        for (int k = 0; k < 15; ++k) w1f[(size_t)n * (F + 16) + F + k] = w1[(size_t)n * IN + F + k];
-    }
-    auto hidden = [](int mt, int r, int kq) { return mt * 16 + 4 * kq + r; };
-    uint16_t *h16 = reinterpret_cast<uint16_t *>(img);
-    lopack.assign(kW1LoPackII, 0.0f);
-    uint16_t *l16 = reinterpret_cast<uint16_t *>(lopack.data());
-    for (int mt = 0; mt < 4; ++mt)
-        for (int kb = 0; kb < L::KB1; ++kb)
-            for (int l = 0; l < 64; ++l)
-                for (int e = 0; e < 8; ++e) {
-                    const int kq = l >> 4, n = mt * 16 + (l & 15), j = kb * 8 + e;
-                    float wv = 0.0f;
-                    if (j < 54) wv = (float)w1f[(size_t)n * (F + 16) + (j / 18) * APPc + infoinv_split_channel(kq * 18 + j % 18)];
-                    else if (j < 58) wv = (float)w1f[(size_t)n * (F + 16) + F + kq * 4 + (j - 54)];      // view entry (entry 15 = zero pad column)
-                    uint16_t p3[3];
-                    split3(wv, p3);
-                    for (int part = 0; part < 2; ++part)
-                        h16[((size_t)L::W1 + ((((size_t)mt * L::KB1 + kb) * 2 + part) * 64 + l) * 4) * 2 + e] = p3[part];
-                    l16[((((size_t)kb * 4 + mt) * 64 + l) * 4) * 2 + e] = p3[2];
-                }
-    for (int mt = 0; mt < 4; ++mt)
-        for (int kb = 0; kb < L::KB2; ++kb)
-            for (int l = 0; l < 64; ++l)
-                for (int e = 0; e < 8; ++e) {
-                    const int kq = l >> 4, n = mt * 16 + (l & 15), j = kb * 8 + e;
-                    uint16_t p3[3];
-                    split3(w2[(size_t)n * 64 + hidden(j >> 2, j & 3, kq)], p3);
-                    for (int part = 0; part < 3; ++part)
-                        h16[((size_t)L::W2 + ((((size_t)mt * L::KB2 + kb) * 3 + part) * 64 + l) * 4) * 2 + e] = p3[part];
-                }
-    for (int kq = 0; kq < 4; ++kq)
-        for (int k = 0; k < 16; ++k) {
-            const int n = hidden(k >> 2, k & 3, kq);
-            img[L::B1 + kq * 16 + k] = b1[n];
-            img[L::B2 + kq * 16 + k] = b2[n];
-            for (int c = 0; c < 3; ++c) img[L::W3 + c * 64 + kq * 16 + k] = w3[(size_t)c * 64 + n];
-        }
-    for (int c = 0; c < 3; ++c) img[L::B3 + c] = b3[c];
-    img[L::B3 + 3] = 0.0f;
-}
-
-// InfoInv default (ngf_infoinv.hpp mlp_pass16_ii): MlpLayout16<72>; k-step t of lane quarter kq is its t-th input -- 18 channels of each
-// plane in the PACKED channel order (infoinv_split_channel), then its 4 view entries
-static void build_rgb_image16_ii(int F, const std::vector<float> &w1p, const std::vector<float> &w1, const std::vector<float> &b1,
-                                 const std::vector<float> &w2, const std::vector<float> &b2, const std::vector<float> &w3, const std::vector<float> &b3,
-                                 float *img)
-{
-    using L = MlpLayout16<72>;
-    const int IN = F + 15, APPc = F / 3;
-    std::vector<double> w1f((size_t)64 * (F + 16), 0.0);       // W1' = [W1[:, :F] . basis | W1[:, F:F+15] | 0]
-    for (int n = 0; n < 64; ++n) {
-        for (int k = 0; k < F; ++k) w1f[(size_t)n * (F + 16) + k] = (double)w1p[(size_t)n * F + k];      // W1[:, :F] . basis, folded on the device (fold_w1_basis_kernel)
-        for (int k = 0; k < 15; ++k) w1f[(size_t)n * (F + 16) + F + k] = w1[(size_t)n * IN + F + k];
-    }
-    auto hidden = [](int mt, int r, int kq) { return mt * 16 + 4 * kq + r; };
-    for (int mt = 0; mt < 4; ++mt)
-        for (int t = 0; t < L::KT; ++t)
-            for (int l = 0; l < 64; ++l) {
-                const int kq = l >> 4, n = mt * 16 + (l & 15);
-                const int col = t < 54 ? (t / 18) * APPc + infoinv_split_channel(kq * 18 + t % 18) : F + kq * 4 + (t - 54);
-                img[L::W1 + ((size_t)mt * L::KT + t) * 64 + l] = (float)w1f[(size_t)n * (F + 16) + col];
-            }
-    for (int mt = 0; mt < 4; ++mt)
-        for (int t = 0; t < 16; ++t)
-            for (int l = 0; l < 64; ++l) img[L::W2 + ((size_t)mt * 16 + t) * 64 + l] = w2[(size_t)(mt * 16 + (l & 15)) * 64 + hidden(t >> 2, t & 3, l >> 4)];
-    for (int kq = 0; kq < 4; ++kq)
-        for (int k = 0; k < 16; ++k) {
-            const int n = hidden(k >> 2, k & 3, kq);
-            img[L::B1 + kq * 16 + k] = b1[n];
-            img[L::B2 + kq * 16 + k] = b2[n];
-            for (int c = 0; c < 3; ++c) img[L::W3 + c * 64 + kq * 16 + k] = w3[(size_t)c * 64 + n];
-        }
-    for (int c = 0; c < 3; ++c) img[L::B3 + c] = b3[c];
-    img[L::B3 + 3] = 0.0f;
-}
-
-// NGF_F_NO_FOLD: layer 1 un-composed, inputs in the accumulator order of the basis stage; basis packed for streaming
-static void build_rgb_image16_nofold(int F, const std::vector<float> &basis, const std::vector<float> &w1, const std::vector<float> &b1,
-                                     const std::vector<float> &w2, const std::vector<float> &b2, const std::vector<float> &w3, const std::vector<float> &b3,
-                                     float *img, std::vector<float> &bpack)
-{
-    using L = MlpLayout16NoFold;
-    const int IN = F + 15, APPc = F / 3, QCH = APPc / 4;
-    auto hidden = [](int mt, int r, int kq) { return mt * 16 + 4 * kq + r; };
-    // layer 1: k-step t < 36 takes g unit (t/4)*16 + 4kq + (t&3); t >= 36 view entry kq*4 + (t-36) (entry 15 = zero pad)
-    for (int mt = 0; mt < 4; ++mt)
-        for (int t = 0; t < L::KT; ++t)
-            for (int l = 0; l < 64; ++l) {
-                const int kq = l >> 4, n = mt * 16 + (l & 15);
-                float wv = 0.0f;
-                if (t < 36) wv = w1[(size_t)n * IN + hidden(t >> 2, t & 3, kq)];
-                else if (kq * 4 + (t - 36) < 15) wv = w1[(size_t)n * IN + F + kq * 4 + (t - 36)];
-                img[L::W1 + ((size_t)mt * L::KT + t) * 64 + l] = wv;
-            }
-    for (int mt = 0; mt < 4; ++mt)
-        for (int t = 0; t < 16; ++t)
-            for (int l = 0; l < 64; ++l)
-                img[L::W2 + ((size_t)mt * 16 + t) * 64 + l] = w2[(size_t)(mt * 16 + (l & 15)) * 64 + hidden(t >> 2, t & 3, l >> 4)];
-    for (int kq = 0; kq < 4; ++kq)
-        for (int k = 0; k < 16; ++k) {
-            const int n = hidden(k >> 2, k & 3, kq);
-            img[L::B1 + kq * 16 + k] = b1[n];
-            img[L::B2 + kq * 16 + k] = b2[n];
-            for (int c = 0; c < 3; ++c) img[L::W3 + c * 64 + kq * 16 + k] = w3[(size_t)c * 64 + n];
-        }
-    for (int c = 0; c < 3; ++c) img[L::B3 + c] = b3[c];
-    img[L::B3 + 3] = 0.0f;
-    // basis stage: k-step t = P*12 + j takes colour channel P*48 + 16*(j/4) + 4kq + (j&3) (the gather order of mlp_pass16);
-    // output unit tile mt (9 tiles), group g = mt/4, element e = mt%4
-    bpack.assign(kBasisPackFloats, 0.0f);
-    for (int t = 0; t < 36; ++t)
-        for (int mt = 0; mt < 9; ++mt)
-            for (int l = 0; l < 64; ++l) {
-                const int kq = l >> 4, j = t % QCH;
-                const int ch = (t / QCH) * APPc + 16 * (j / 4) + 4 * kq + (j & 3);
-                bpack[(((size_t)t * 3 + mt / 4) * 64 + l) * 4 + (mt & 3)] = basis[(size_t)(mt * 16 + (l & 15)) * F + ch];
-            }
-}
-
-static void build_rgb_image16(int F, bool bake, const std::vector<float> &w1p, const std::vector<float> &w1, const std::vector<float> &b1,
-                              const std::vector<float> &w2, const std::vector<float> &b2, const std::vector<float> &w3,
-                              const std::vector<float> &b3, float *img)
-{
-    const int IN = F + 15, APPc = F / 3, QCH = APPc / 4, KT = 3 * QCH + 4;
-    std::vector<double> w1f((size_t)64 * (F + 16), 0.0);       // W1' = [W1[:, :F] . basis | W1[:, F:F+15] | 0]
-    for (int n = 0; n < 64; ++n) {
-        for (int k = 0; k < F; ++k) w1f[(size_t)n * (F + 16) + k] = (double)w1p[(size_t)n * F + k];      // W1[:, :F] . basis, folded on the device (fold_w1_basis_kernel)
-        for (int k = 0; k < 15; ++k) w1f[(size_t)n * (F + 16) + F + k] = w1[(size_t)n * IN + F + k];
-    }
-    auto hidden = [](int mt, int r, int kq) { return mt * 16 + 4 * kq + r; };
-    int oW1, oW2, oB1, oB2, oW3, oB3;
-    if (bake) {
-        using L = MlpLayout16Baked;
-        oW1 = L::W1V; oW2 = L::W2; oB1 = L::B1; oB2 = L::B2; oW3 = L::W3; oB3 = L::B3;
-        for (int mt = 0; mt < 4; ++mt)
-            for (int j = 0; j < 4; ++j)
-                for (int l = 0; l < 64; ++l)
-                    img[oW1 + ((size_t)mt * 4 + j) * 64 + l] = (float)w1f[(size_t)(mt * 16 + (l & 15)) * (F + 16) + F + (l >> 4) * 4 + j];
-    } else {
-        using L = MlpLayout16<48>;
-        oW1 = L::W1; oW2 = L::W2; oB1 = L::B1; oB2 = L::B2; oW3 = L::W3; oB3 = L::B3;
-        auto kmap = [&](int t, int kq) {
-            if (t < 3 * QCH) return (t / QCH) * APPc + 16 * ((t % QCH) / 4) + 4 * kq + ((t % QCH) & 3);   // channel 16q + 4kq + e
-            return F + kq * 4 + (t - 3 * QCH);
-        };
-        for (int mt = 0; mt < 4; ++mt)
-            for (int t = 0; t < KT; ++t)
-                for (int l = 0; l < 64; ++l)
-                    img[oW1 + ((size_t)mt * KT + t) * 64 + l] = (float)w1f[(size_t)(mt * 16 + (l & 15)) * (F + 16) + kmap(t, l >> 4)];
-    }
-    for (int mt = 0; mt < 4; ++mt)
-        for (int t = 0; t < 16; ++t)
-            for (int l = 0; l < 64; ++l)
-                img[oW2 + ((size_t)mt * 16 + t) * 64 + l] = w2[(size_t)(mt * 16 + (l & 15)) * 64 + hidden(t >> 2, t & 3, l >> 4)];
-    for (int kq = 0; kq < 4; ++kq)
-        for (int k = 0; k < 16; ++k) {
-            const int n = hidden(k >> 2, k & 3, kq);
-            img[oB1 + kq * 16 + k] = b1[n];
-            img[oB2 + kq * 16 + k] = b2[n];
-            for (int c = 0; c < 3; ++c) img[oW3 + c * 64 + kq * 16 + k] = w3[(size_t)c * 64 + n];
-        }
-    for (int c = 0; c < 3; ++c) img[oB3 + c] = b3[c];
-    img[oB3 + 3] = 0.0f;
-}
-
 
 // ---- buffer pool of the field handles (round 5) ---------------------------------------------------------------------------------
 // A handle is rebuilt after every parameter change of an eval field (Base.handle()): same shapes, so the same ten buffer sizes.  hipFree
@@ -816,15 +535,14 @@ extern "C" int ngf_field_create(const ngf_field_desc *d, ngf_field **out, void *
     const bool bake_c = tri && (d->flags & NGF_F_BAKE_COLOR);
     const bool no_fold = tri && (d->flags & NGF_F_NO_FOLD);
     const bool split_bf16 = tri && (d->flags & NGF_F_SPLIT_BF16);
-    const bool split_ii = !tri && (d->flags & NGF_F_SPLIT_BF16);
     if (no_fold && (bake || bake_c)) return bail(fail(NGF_E_ARG, "NGF_F_NO_FOLD is the un-composed formulation: it excludes the NGF_F_BAKE_* flags"));
     if (split_bf16 && no_fold) return bail(fail(NGF_E_ARG, "NGF_F_SPLIT_BF16 applies to the pre-composed formulations (not with NGF_F_NO_FOLD)"));
     if (split_bf16 && bake_c && !bake) return bail(fail(NGF_E_ARG, "NGF_F_BAKE_COLOR | NGF_F_SPLIT_BF16 (level 3 with layer 2 on the bf16 matrix pipe) is built on top of NGF_F_BAKE_DENSITY"));
-    const bool split_l3 = split_bf16 && bake_c;        // round 5: level 3, layer 2 as split bf16 products (layer 1 is folded into the planes there)
 
     // MLP weights: to the host once, pre-compose, permute, back to HBM as one LDS image
     // W1' = W1[:, :F] . basis comes folded from the device (fold_w1_basis_kernel) for every formulation that pre-composes it; level 0 streams basis itself
-    std::vector<float> basis, w1p, w1, b1, w2, b2, w3, b3;
+    FieldWeights Wt;
+    std::vector<float> &basis = Wt.basis, &w1p = Wt.w1p, &w1 = Wt.w1, &b1 = Wt.b1, &w2 = Wt.w2, &b2 = Wt.b2, &w3 = Wt.w3, &b3 = Wt.b3;
     if (!d->basis || !d->w1) return bail(fail(NGF_E_ARG, "missing weight tensor"));
     if (no_fold) {
         if ((rc = d2h(basis, d->basis, (size_t)F * F, st))) return bail(rc);
@@ -838,7 +556,7 @@ extern "C" int ngf_field_create(const ngf_field_desc *d, ngf_field **out, void *
         (rc = d2h(b1, d->b1, 64, st)) || (rc = d2h(w2, d->w2, 64 * 64, st)) || (rc = d2h(b2, d->b2, 64, st)) ||
         (rc = d2h(w3, d->w3, 3 * 64, st)) || (rc = d2h(b3, d->b3, 3, st)))
         return bail(rc);
-    std::vector<float> dw1, db1, dw2, db2, dw3, db3;
+    std::vector<float> &dw1 = Wt.dw1, &db1 = Wt.db1, &dw2 = Wt.dw2, &db2 = Wt.db2, &dw3 = Wt.dw3, &db3 = Wt.db3;
     if (tri) {
         if ((rc = d2h(dw1, d->dens_w1, 48, st)) || (rc = d2h(db1, d->dens_b1, 1, st))) return bail(rc);
     } else {
@@ -850,28 +568,15 @@ extern "C" int ngf_field_create(const ngf_field_desc *d, ngf_field **out, void *
     if (hipStreamSynchronize(st) != hipSuccess) return bail(fail(NGF_E_HIP, "hipStreamSynchronize failed in ngf_field_create"));
     NGF_CT("fold kernel + D2H + sync");
 
-    const int rgb_floats = tri ? (split_l3 ? MlpLayout16BakedBf16::TOTAL : split_bf16 ? MlpLayoutBf16::TOTAL : no_fold ? MlpLayout16NoFold::TOTAL : (bake_c ? MlpLayout16Baked::TOTAL : MlpLayout16<48>::TOTAL)) : (split_ii ? MlpLayoutBf16II::TOTAL : MlpLayout16<72>::TOTAL);
-    const int dens_floats = tri ? 0 : (split_ii ? InfoInvDensLayoutBf16::TOTAL : InfoInvDensLayout::TOTAL);
-    std::vector<float> img((size_t)rgb_floats + dens_floats, 0.0f);
-    std::vector<float> bpack;
-    if (split_l3) {
-        std::vector<float> baked((size_t)MlpLayout16Baked::TOTAL, 0.0f);
-        build_rgb_image16(F, true, w1p, w1, b1, w2, b2, w3, b3, baked.data());
-        rebuild_baked_image_bf16(baked, w2, img.data());
-    } else if (split_bf16) build_rgb_image_bf16(F, w1p, w1, b1, w2, b2, w3, b3, img.data());
-    else if (no_fold) build_rgb_image16_nofold(F, basis, w1, b1, w2, b2, w3, b3, img.data(), bpack);
-    else if (tri) build_rgb_image16(F, bake_c, w1p, w1, b1, w2, b2, w3, b3, img.data());
-    else if (split_ii) build_rgb_image_bf16_ii(F, w1p, w1, b1, w2, b2, w3, b3, img.data(), bpack);
-    else build_rgb_image16_ii(F, w1p, w1, b1, w2, b2, w3, b3, img.data());
-    if (!tri && split_ii) build_infoinv_density_image_bf16(dw1, db1, dw2, db2, dw3, db3, img.data() + rgb_floats);
-    else if (!tri) build_infoinv_density_image(dw1, db1, dw2, db2, dw3, db3, img.data() + rgb_floats);
+    std::vector<float> img, bpack;          // the LDS image (colour, then InfoInv's density MLP) and the matrix the shade streams from L2
+    build_field_images(d->model, d->flags, Wt, img, bpack);
     NGF_CT("host images");
     if ((rc = alloc_f(&f->blob, img.size(), f, st))) return bail(rc);
     if (hipMemcpyAsync(f->blob, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess)
         return bail(fail(NGF_E_HIP, "uploading the MLP image failed"));
     A.blob = f->blob;
     A.blob_floats = (int)img.size();
-    if (no_fold || split_ii) {        // the matrix the shade streams from L2 (level-0 basis / lo parts of InfoInv's split layer 1)
+    if (!bpack.empty()) {        // the matrix the shade streams from L2 (level-0 basis / lo parts of InfoInv's split layer 1)
         if ((rc = alloc_f(&f->basis_pack, bpack.size(), f, st))) return bail(rc);
         if (hipMemcpyAsync(f->basis_pack, bpack.data(), bpack.size() * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess)
             return bail(fail(NGF_E_HIP, "uploading the packed basis matrix failed"));

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ngf_mlp_layout.hpp"      // InfoInvDensLayout, InfoInvDensLayoutBf16, MlpLayoutBf16II, kW1LoPackII, infoinv_split_channel
 #include "ngf_render.hpp"
 
 namespace ngf {
@@ -22,95 +23,6 @@ constexpr int kInfoInvWaves = 12;
                                   // spills at the 168 registers of twelve waves per CU; 3: 32 and none -- same speed in an alternating A/B, profiles/r04_infoinv_tap_parts.txt)
 #endif
 constexpr int kInfoInvSplitWaves = 8;        // NGF_F_SPLIT_BF16: 102 KB of MLP images + 5.4 KB per wave
-
-struct InfoInvDensLayout {                  // floats, relative to MlpLayout16<72>::TOTAL inside the blob
-    static constexpr int D1 = 0;                    // [36 k-steps][64 lanes] : W1[l&31][2t + (l>>5)]
-    static constexpr int D2 = D1 + 36 * 64;         // [16 k-steps][64 lanes] : W2[l&31][row(t, l>>5)]
-    static constexpr int B1 = D2 + 16 * 64;         // [2 hi][16]
-    static constexpr int B2 = B1 + 32;              // [2 hi][16]
-    static constexpr int W3 = B2 + 32;              // [2 hi][16]
-    static constexpr int B3 = W3 + 32;              // [4]
-    static constexpr int TOTAL = B3 + 4;
-};
-
-inline void build_infoinv_density_image(const std::vector<float> &w1, const std::vector<float> &b1, const std::vector<float> &w2,
-                                        const std::vector<float> &b2, const std::vector<float> &w3, const std::vector<float> &b3,
-                                        float *img)
-{
-    using D = InfoInvDensLayout;
-    for (int t = 0; t < 36; ++t)
-        for (int l = 0; l < 64; ++l) img[D::D1 + t * 64 + l] = w1[(size_t)(l & 31) * 72 + 2 * t + (l >> 5)];
-    for (int t = 0; t < 16; ++t)
-        for (int l = 0; l < 64; ++l) img[D::D2 + t * 64 + l] = w2[(size_t)(l & 31) * 32 + ((t & 3) + 8 * (t >> 2) + 4 * (l >> 5))];
-    for (int hi = 0; hi < 2; ++hi)
-        for (int r = 0; r < 16; ++r) {
-            const int n = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            img[D::B1 + hi * 16 + r] = b1[n];
-            img[D::B2 + hi * 16 + r] = b2[n];
-            img[D::W3 + hi * 16 + r] = w3[n];
-        }
-    img[D::B3] = b3[0];
-    img[D::B3 + 1] = img[D::B3 + 2] = img[D::B3 + 3] = 0.0f;
-}
-
-// NGF_F_SPLIT_BF16: the density MLP of the march on v_mfma_f32_32x32x16_bf16 with 3-term split operands (sigma_bf16 below).
-// A fragments: lane (i = l & 31, hi = l >> 5), element e of k-block kb holds W[i][16 kb + 8 hi + e] -- layer 1 over the 72 inputs in
-// their natural order (plane p, channel c -> 24 p + c; 8 zero pads), layer 2 over the hidden units in the accumulator order of the lane
-// half (k = 8 q + e  ->  unit (k & 3) + 8 (k >> 2) + 4 hi), so that a lane's own ReLU'd accumulators are its B fragments.
-struct InfoInvDensLayoutBf16 {              // floats (a bf16x8 fragment = 4 floats), relative to MlpLayoutBf16II::TOTAL inside the blob
-    static constexpr int KB1 = 5, KB2 = 2;
-    static constexpr int D1 = 0;                    // [5 kb][3 parts][64 lanes][4]
-    static constexpr int D2 = D1 + KB1 * 3 * 64 * 4;   // [2 kb][3 parts][64 lanes][4]
-    static constexpr int B1 = D2 + KB2 * 3 * 64 * 4;   // [2 hi][16]
-    static constexpr int B2 = B1 + 32;
-    static constexpr int W3 = B2 + 32;
-    static constexpr int B3 = W3 + 32;
-    static constexpr int TOTAL = B3 + 4;
-};
-
-inline void infoinv_split3(float x, uint16_t out[3])
-{
-    auto f2bf = [](float v) { uint32_t u; memcpy(&u, &v, 4); const uint32_t r = 0x7fffu + ((u >> 16) & 1u); return (uint16_t)((u + r) >> 16); };
-    auto bf2f = [](uint16_t h) { const uint32_t u = (uint32_t)h << 16; float v; memcpy(&v, &u, 4); return v; };
-    out[0] = f2bf(x);
-    const float r1 = x - bf2f(out[0]);
-    out[1] = f2bf(r1);
-    const float r2 = r1 - bf2f(out[1]);
-    out[2] = f2bf(r2);
-}
-
-inline void build_infoinv_density_image_bf16(const std::vector<float> &w1, const std::vector<float> &b1, const std::vector<float> &w2,
-                                             const std::vector<float> &b2, const std::vector<float> &w3, const std::vector<float> &b3,
-                                             float *img)
-{
-    using D = InfoInvDensLayoutBf16;
-    uint16_t *h16 = reinterpret_cast<uint16_t *>(img);
-    auto unit = [](int k, int hi) { return (k & 3) + 8 * (k >> 2) + 4 * hi; };
-    for (int kb = 0; kb < D::KB1; ++kb)
-        for (int l = 0; l < 64; ++l)
-            for (int e = 0; e < 8; ++e) {
-                const int k = 16 * kb + 8 * (l >> 5) + e;
-                uint16_t p3[3];
-                infoinv_split3(k < 72 ? w1[(size_t)(l & 31) * 72 + k] : 0.0f, p3);
-                for (int part = 0; part < 3; ++part) h16[((size_t)D::D1 + (((size_t)kb * 3 + part) * 64 + l) * 4) * 2 + e] = p3[part];
-            }
-    for (int q = 0; q < D::KB2; ++q)
-        for (int l = 0; l < 64; ++l)
-            for (int e = 0; e < 8; ++e) {
-                uint16_t p3[3];
-                infoinv_split3(w2[(size_t)(l & 31) * 32 + unit(8 * q + e, l >> 5)], p3);
-                for (int part = 0; part < 3; ++part) h16[((size_t)D::D2 + (((size_t)q * 3 + part) * 64 + l) * 4) * 2 + e] = p3[part];
-            }
-    for (int hi = 0; hi < 2; ++hi)
-        for (int r = 0; r < 16; ++r) {
-            const int n = unit(r, hi);
-            img[D::B1 + hi * 16 + r] = b1[n];
-            img[D::B2 + hi * 16 + r] = b2[n];
-            img[D::W3 + hi * 16 + r] = w3[n];
-        }
-    img[D::B3] = b3[0];
-    img[D::B3 + 1] = img[D::B3 + 2] = img[D::B3 + 3] = 0.0f;
-}
 
 // One octave step of the positional factors: f_s *= sin, f_c *= cos, then the angle doubling (sin 2a = 2 sin cos, cos 2a = (cos - sin)(cos + sin)).
 // Written as SINGLE VALU instructions on purpose.  hipcc 7.2 packs the plain C++ form of this chain into v_pk_mul_f32 / v_pk_add_f32 with
@@ -160,24 +72,7 @@ __device__ __forceinline__ void swap32(float &a, float &b)
 //     + w11 v11), so the features are bit-identical to the fp32 path's and 36 registers of gather are in flight instead of 72.
 // The first version of this flag (two lanes per sample on v_mfma_f32_32x32x16_bf16, layer 1 streamed from L2) was register-bound and
 // not faster (profiles/r02_infoinv_split.txt).
-struct MlpLayoutBf16II {                      // LDS image (floats); a bf16x8 fragment = 4 floats
-    static constexpr int KB1 = 8, KB2 = 2;
-    static constexpr int W1 = 0;                              // [4 mt][8 kb][2 parts: hi, mid][64 lanes][4]
-    static constexpr int W2 = W1 + 4 * KB1 * 2 * 64 * 4;      // [4 mt][2 kb][3 parts][64 lanes][4]
-    static constexpr int B1 = W2 + 4 * KB2 * 3 * 64 * 4;      // [4 kq][16] fp32, accumulator order
-    static constexpr int B2 = B1 + 64;
-    static constexpr int W3 = B2 + 64;                        // [3][4 kq][16]
-    static constexpr int B3 = W3 + 192;
-    static constexpr int TOTAL = B3 + 4;
-};
-constexpr int kW1LoPackII = MlpLayoutBf16II::KB1 * 4 * 64 * 4;      // floats of the streamed image: layer 1's lo parts [kb][mt][lane][8 bf16]
-// packed position (0..71) of a plane's colour channels -> channel of the reference layout
-__host__ __device__ __forceinline__ int infoinv_split_channel(int pos)
-{
-    const int kq = pos / 18, r = pos % 18, g = r / 3, j = r % 3;        // g = hi*3 + axis
-    return (g / 3) * 36 + (g % 3) * 12 + 3 * kq + j;
-}
-
+// (MlpLayoutBf16II, kW1LoPackII and infoinv_split_channel: ngf_mlp_layout.hpp)
 struct GatherRowII { f32x4 a[2][4]; f32x2 b[2]; };               // one row of a cell: two taps x 18 channels (36 registers)
 __device__ __forceinline__ void gather_row_ii(const float *base, GatherRowII &g)
 {

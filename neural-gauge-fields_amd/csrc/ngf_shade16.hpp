@@ -15,6 +15,7 @@
 #include <utility>
 
 #include "ngf_device.hpp"
+#include "ngf_mlp_layout.hpp"      // MlpLayout16<>, MlpLayout16Baked, MlpLayout16BakedBf16, MlpLayout16NoFold, kBasisPackFloats
 
 namespace ngf {
 
@@ -24,42 +25,6 @@ constexpr int kBatch16 = 16;
 // (19.6 % of the LDS-active cycles of the level-3 launch were bank conflicts, profiles/r04_triplane_R1_bdc_pmc.txt); a multiple of 4 keeps the
 // 16-byte reads of levels 1-2 aligned.
 constexpr int kFoldStride = 68;
-
-template <int APP>
-struct MlpLayout16 {                      // floats
-    static constexpr int QCH = APP / 4;           // colour channels per plane per lane (12)
-    static constexpr int KT = 3 * QCH + 4;        // layer-1 k-steps, 4 inputs each (40)
-    static constexpr int W1 = 0;                  // [4 mt][KT][64 lanes]
-    static constexpr int W2 = W1 + 4 * KT * 64;   // [4 mt][16][64 lanes]
-    static constexpr int B1 = W2 + 4 * 16 * 64;   // [4 kq][16]
-    static constexpr int B2 = B1 + 64;
-    static constexpr int W3 = B2 + 64;            // [3][4 kq][16]
-    static constexpr int B3 = W3 + 192;
-    static constexpr int TOTAL = B3 + 4;
-};
-
-struct MlpLayout16Baked {                 // NGF_F_BAKE_COLOR: only the view-input k-steps of layer 1 remain
-    static constexpr int W1V = 0;                 // [4 mt][4][64 lanes]
-    static constexpr int W2 = W1V + 4 * 4 * 64;
-    static constexpr int B1 = W2 + 4 * 16 * 64;
-    static constexpr int B2 = B1 + 64;
-    static constexpr int W3 = B2 + 64;
-    static constexpr int B3 = W3 + 192;
-    static constexpr int TOTAL = B3 + 4;
-};
-
-// NGF_F_BAKE_COLOR | NGF_F_SPLIT_BF16 (round 5, opt-in): level 3 with LAYER 2 on the bf16 matrix pipe as 3-term split products (ngf_shade_bf16.hpp
-// mlp_pass16_baked_bf16).  Same front part as MlpLayout16Baked (the view-input k-steps at offset 0), then W2 as bf16 A fragments
-// [4 mt][2 k-blocks][3 parts][64 lanes][8 bf16] (= 4 floats per fragment), then the fp32 tables.
-struct MlpLayout16BakedBf16 {
-    static constexpr int W1V = 0;                 // [4 mt][4][64 lanes] fp32
-    static constexpr int W2 = W1V + 4 * 4 * 64;   // bf16 fragments: 4 x 2 x 3 x 64 x 4 floats
-    static constexpr int B1 = W2 + 4 * 2 * 3 * 64 * 4;
-    static constexpr int B2 = B1 + 64;
-    static constexpr int W3 = B2 + 64;
-    static constexpr int B3 = W3 + 192;
-    static constexpr int TOTAL = B3 + 4;
-};
 
 __device__ __forceinline__ const float *per_pass16(const float *blob)
 {
@@ -301,17 +266,7 @@ __device__ __forceinline__ void mlp_pass16(const RenderArgs &A, const float *blo
 // The basis matrix (83 KB) does not fit LDS next to the layers: it is streamed from L2 as [k-step][3 tile groups][lane][4] (one
 // 16-byte load feeds four MFMAs).  The 144 outputs land in accumulator order (unit mt*16 + 4*kq + r of the lane's own sample),
 // which is the B operand order of the next layer, so layer 1 consumes them in place.
-struct MlpLayout16NoFold {                 // LDS image (floats): layer 1 on [g(144) | view(16)] in accumulator order, then as MlpLayout16
-    static constexpr int KT = 40;
-    static constexpr int W1 = 0;                  // [4 mt][40][64]
-    static constexpr int W2 = W1 + 4 * KT * 64;
-    static constexpr int B1 = W2 + 4 * 16 * 64;
-    static constexpr int B2 = B1 + 64;
-    static constexpr int W3 = B2 + 64;
-    static constexpr int B3 = W3 + 192;
-    static constexpr int TOTAL = B3 + 4;
-};
-constexpr int kBasisPackFloats = 36 * 3 * 64 * 4;      // [36 k-steps][3 groups of 4 unit tiles (9 used)][64 lanes][4]
+// (MlpLayout16NoFold, the LDS image of layers 1-3, and kBasisPackFloats: ngf_mlp_layout.hpp)
 
 struct BasisPair { f32x4 a[2][3]; };              // A operands of two k-steps (9 unit tiles in 3 groups of 4)
 

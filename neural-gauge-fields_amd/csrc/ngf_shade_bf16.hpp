@@ -14,22 +14,12 @@
 //   layer 3  64 -> 3 on the fp32 VALU as in mlp_tail16 (48 FMAs per lane: no matrix work worth splitting)
 // A fragments (weights, pre-split on the host, layer 1 pre-composed with `basis`) live in LDS as [mt][k-block][part][lane][8 bf16].
 #pragma once
+#include "ngf_mlp_layout.hpp"      // MlpLayoutBf16
 #include "ngf_shade16.hpp"
 
 namespace ngf {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
-
-struct MlpLayoutBf16 {                        // floats (a bf16x8 fragment = 4 floats)
-    static constexpr int KB1 = 5, KB2 = 2;
-    static constexpr int W1 = 0;                              // [4 mt][5 kb][3 parts][64 lanes][4]
-    static constexpr int W2 = W1 + 4 * KB1 * 3 * 64 * 4;      // [4 mt][2 kb][3 parts][64 lanes][4]
-    static constexpr int B1 = W2 + 4 * KB2 * 3 * 64 * 4;      // [4 kq][16] fp32, accumulator order
-    static constexpr int B2 = B1 + 64;
-    static constexpr int W3 = B2 + 64;                        // [3][4 kq][16] fp32
-    static constexpr int B3 = W3 + 192;
-    static constexpr int TOTAL = B3 + 4;
-};
 
 struct Split8 { bf16x8 h, m, l; };
 

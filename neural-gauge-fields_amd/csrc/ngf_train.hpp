@@ -466,7 +466,7 @@ constexpr int kBwdTileFloats = 16 * kDfStride + 64 * kTs;
 static_assert(16 * kDfStride >= 2 * 64 * kTs, "DF^T must cover the H1 and D2 tiles it aliases");
 
 // ---- per-step weight images -------------------------------------------------------------------------------------------------
-// fwd16 (round 5): the same W1' / W2 / W3 / biases in the eval pass's image layout MlpLayout16<48> (ngf_shade16.hpp: what build_rgb_image16 makes on
+// fwd16 (round 5): the same W1' / W2 / W3 / biases in the eval pass's image layout MlpLayout16<48> (ngf_mlp_layout.hpp: what build_field_images makes on
 // the host for a render handle) -- A operands [unit tile][k-step][lane], lane (i, kq) of k-step t = input kmap(t, kq) of unit mt * 16 + i;
 // hidden units in accumulator order n = mt * 16 + 4 kq + r.
 __global__ void __launch_bounds__(256) train_fold_kernel(const TrainArgs T, float *fwd, float *bwd, float *fwd16)

@@ -1,5 +1,6 @@
 // ngf_uv.hip -- C ABI (include/ngf.h), UV-Mapping (NeuTex) part: weight packing, render, texture editing.
 #include "ngf_host.hpp"
+#include "ngf_mlp_image.hpp"      // split3, hidden: shared with the field images
 #include "ngf_uv.hpp"
 
 using namespace ngf;
@@ -29,7 +30,7 @@ extern "C" int ngf_uv_destroy(ngf_uv *m)
 namespace {
 struct UvPacker {
     std::vector<float> buf;
-    static int hidden(int t, int kq) { return (t >> 2) * 16 + 4 * kq + (t & 3); }
+    static int hidden(int t, int kq) { return ngf::hidden(t >> 2, t & 3, kq); }      // the previous layer's unit behind k-step t of lane quarter kq
     int align() { while (buf.size() & 3) buf.push_back(0.0f); return (int)buf.size(); }
     // imap(t, kq) -> input index (or -1); KT k-steps; NT unit tiles (multiple of 4)
     template <typename F>
@@ -61,20 +62,6 @@ struct UvPacker {
     }
     // split-bf16 image of a 256-unit layer: [KB][4 groups][3 parts][4 tiles][64 lanes][8 bf16]; imap(j, kq) = input index of the lane
     // quarter's j-th input (j = 8 kb + e), as in dense()
-    static uint16_t f2bf(float x)
-    {
-        uint32_t u;
-        memcpy(&u, &x, 4);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-        return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    }
-    static float bf2f(uint16_t h)
-    {
-        const uint32_t u = (uint32_t)h << 16;
-        float f;
-        memcpy(&f, &u, 4);
-        return f;
-    }
     template <typename F>
     int dense_bf16(const std::vector<float> &W, int out_f, int in_f, int KB, F imap)
     {
@@ -89,10 +76,7 @@ struct UvPacker {
                             const int o = (4 * g + e) * 16 + (l & 15), i = imap(kb * 8 + ee, l >> 4);
                             const float wv = (o < out_f && i >= 0 && i < in_f) ? W[(size_t)o * in_f + i] : 0.0f;
                             uint16_t p3[3];
-                            p3[0] = f2bf(wv);
-                            const float r1 = wv - bf2f(p3[0]);
-                            p3[1] = f2bf(r1);
-                            p3[2] = f2bf(r1 - bf2f(p3[1]));
+                            split3(wv, p3);
                             for (int part = 0; part < 3; ++part)
                                 h16[(((((size_t)kb * 4 + g) * 3 + part) * 4 + e) * 64 + l) * 8 + ee] = p3[part];
                         }
