@@ -147,7 +147,13 @@ class library:
     knob state: handles created inside the block must be used and released inside it.  Tests and profiles/ scripts only."""
 
     def __init__(self, which="exp"):
-        self.path = SO_PATH_EXP if which == "exp" else SO_PATH
+        # "exp" | "product" | the path of another build of the library (make exp NAME=...: the A/B scripts under profiles/)
+        if which == "exp":
+            self.path = SO_PATH_EXP
+        elif which == "product" or not os.path.isfile(which):
+            self.path = SO_PATH
+        else:
+            self.path = os.path.abspath(which)
 
     def __enter__(self):
         global _LIB

@@ -750,7 +750,7 @@ extern "C" int ngf_debug_tile_plan(int64_t n, int32_t wide, int64_t resident, in
 // kernel / kernel_split: the DBG = true instantiations (every feature); kernel_prod: the split kernel's production instantiation (no debug
 // outputs, ablation bits, statistics: render_kernel<P, true, false>) or null when the policy has none
 template <typename K>
-static int launch_render(K kernel, K kernel_split, K kernel_prod, const ngf_field *f, RenderArgs &A, int threads, size_t lds_bytes, hipStream_t st, int wide_tile)
+static int launch_render(K kernel, K kernel_split, K kernel_prod, const ngf_field *f, RenderArgs &A, int threads, size_t lds_bytes, hipStream_t st, int wide_tile, int max_split_shift = 6)
 {
     // the slot's queue heads are zero: ngf_field_create zeroed all slots, and the last wave of every launch zeroes its slot again (queue_done)
     const unsigned slot = f->next_counter.fetch_add(1) % kCounters;
@@ -787,6 +787,11 @@ static int launch_render(K kernel, K kernel_split, K kernel_prod, const ngf_fiel
     } else {
         nseg = make_tile_plan(A.n, wide_tile, resident, knob(KNOB_TAIL) >= 0 ? knob(KNOB_TAIL) : kTailDefault16, seg_rays, seg_shift);
     }
+    // a split kernel whose collect knows the lane patterns of narrow tiles only (TriPlanePolicy::COLLECT3: 8, 4, 2, 1 rays) must never see a wider one: it would
+    // add colours into the wrong lanes without any error.  level3_waves16 keeps such launches on the twelve-wave kernel; this is the check behind it.
+    if (split)
+        for (int k = 0; k < nseg; ++k)
+            if (seg_shift[k] > max_split_shift) return fail(NGF_E_ARG, "this kernel renders split tiles of at most %d rays (plan segment %d has %d)", 1 << max_split_shift, k, 1 << seg_shift[k]);
     A.tile_shift = seg_shift[0];
     A.tile_w = 1 << seg_shift[0];
     int64_t tiles = 0, ray0 = 0;
@@ -860,7 +865,9 @@ static int launch_policy(const ngf_field *f, RenderArgs &A, hipStream_t st)
     if (lds > 160 * 1024) return fail(NGF_E_ARG, "this waves-per-CU setting needs %zu bytes of LDS (> 160 KiB)", lds);
     constexpr int wide = P::INFOINV ? 16 : 8;          // measured best full-frame tile width (profiles/r01_split_march.txt; InfoInv: 30.3 vs 29.3 Mray/s)
     using KP = decltype(&render_kernel<P, false>);
-    if constexpr (P::NSTEP == 1 && P::PROD) return launch_render<KP>(render_kernel<P, false>, render_kernel<P, true>, render_kernel<P, true, false>, f, A, P::WAVES * kWave, lds, st, wide);
+    constexpr int max_shift = collect3<P>::value ? 3 : 6;          // COLLECT3: the three-lane collect has the lane patterns of tiles of <= 8 rays
+    static_assert(!collect3<P>::value || wide <= 8, "the plan's widest tile must be one the three-lane collect knows");
+    if constexpr (P::NSTEP == 1 && P::PROD) return launch_render<KP>(render_kernel<P, false>, render_kernel<P, true>, render_kernel<P, true, false>, f, A, P::WAVES * kWave, lds, st, wide, max_shift);
     else if constexpr (P::NSTEP == 1) return launch_render<KP>(render_kernel<P, false>, render_kernel<P, true>, nullptr, f, A, P::WAVES * kWave, lds, st, wide);
     else return launch_render<KP>(render_kernel<P, false>, nullptr, nullptr, f, A, P::WAVES * kWave, lds, st, wide);
 }
@@ -912,6 +919,11 @@ static bool level3_waves16(const ngf_field *f, const RenderArgs &A)
     static_assert(P::W16 && P::PROD && P::REC12 && P::VLDS && P::VIEW_FOLD, "the sixteen-wave level-3 policy is the production pass");
     const size_t lds = ((size_t)((A.blob_floats + 3) & ~3) + P::WAVES * wave_lds_floats<P>()) * sizeof(float);
     if (lds > 160 * 1024) return false;
+    // COLLECT3: the sixteen-wave split kernel keeps a ray's three colour sums in three of its lanes and knows the lane patterns of the plan's widths
+    // (8, 4, 2, 1 rays); split tiles of 16 / 32 / 64 rays (the tile_w knob alone makes them) keep the twelve-wave kernel, like a field that does not
+    // fit.  (tile_w = 64 without the split knob is the unsplit kernel, one lane per ray and the v_cmpx collect, at either wave count.)
+    const int tw = knob(KNOB_TILE_W);
+    if (collect3<P>::value && (tw == 16 || tw == 32 || (tw == 64 && knob(KNOB_SPLIT) > 0))) return false;
     if (knob(KNOB_WAVES) >= 0) return knob(KNOB_WAVES) == 16;
     return A.n >= kW16MinRaysPerCu * f->num_cus;
 }

@@ -250,6 +250,13 @@ struct TriPlanePolicy {
     // parts, in-range bit) instead of its six coordinates, so a shade pass starts its gathers at once and spends 8 instead of ~28 instructions per
     // plane on the cell -- all 64 lanes of a pass used to redo the three setups of their 16 samples that the march had already done.
     static constexpr bool REC12 = (WAVES_ == 12 || W16) && NSTEP_ == 1 && !PROFILE_;
+    // COLLECT3 (the sixteen-wave level-3 policy): the owner collect of a shade pass without v_cmpx -- a ray's three colour sums live in its seg-0, 1, 2
+    // lanes, an entry's three-lane EXEC mask is made on the scalar unit and the entry is ONE v_add_f32 (render_kernel, behind the result list)
+#ifdef NGF_NO_COLLECT3
+    static constexpr bool COLLECT3 = false;                     // A/B builds (profiles/r11_simd_trim.txt): the sixteen-wave kernel with the v_cmpx collect
+#else
+    static constexpr bool COLLECT3 = W16;
+#endif
     static constexpr bool GATHER_QUAD = BAKE_C;                 // the shade's gather lane 4 s + kq works for sample lane >> 2 (ngf_shade16.hpp mlp_pass16_baked): shade12 takes ITS cells
     static constexpr bool SHARED_GAUGE = BAKE_D;                 // sigma() takes the shared-axis gauge set-up: launched only for RenderArgs::gauge_same, GaugeAny<P> otherwise
     template <bool SAME>
@@ -338,6 +345,8 @@ struct GaugeAny : P {
 };
 template <typename P, typename = void> struct shared_gauge : std::false_type {};
 template <typename P> struct shared_gauge<P, std::void_t<decltype(P::SHARED_GAUGE)>> : std::integral_constant<bool, P::SHARED_GAUGE> {};
+template <typename P, typename = void> struct collect3 : std::false_type {};
+template <typename P> struct collect3<P, std::void_t<decltype(P::COLLECT3)>> : std::integral_constant<bool, P::COLLECT3> {};
 
 // NGF_F_SPLIT_BF16: the colour MLP on the bf16 matrix pipe with 3-term split operands (ngf_shade_bf16.hpp).  Split tiles of <= 8 rays
 // only (the wave keeps the view inputs of 8 rays); 8 waves per CU (the pass needs ~200 registers).
@@ -832,7 +841,9 @@ __global__ void __launch_bounds__(P::WAVES * 64) render_kernel(const RenderArgs 
                 // result list, structure-of-arrays: res[0..B) owner lane ids, then weighted r, g, b
                 // c[] holds the three logits in all four lanes of a sample: lane quarter kq applies the sigmoid to channel kq and writes that entry of
                 // the list (res[(1 + kq) * BATCH + s] is res[BATCH + lane]) -- one sigmoid per lane instead of three
-                if (lane < BATCH) res[lane] = lane < nb ? __int_as_float(owner_lane) : __int_as_float(-1);
+                // COLLECT3 (the sixteen-wave level-3 policy): the owner ids go to SGPRs instead (below), the list holds the colours only
+                constexpr bool C3 = SPLIT && collect3<P>::value;
+                if (!C3 && lane < BATCH) res[lane] = lane < nb ? __int_as_float(owner_lane) : __int_as_float(-1);
                 if (lane < 3 * BATCH) {
                     const int kq_ = lane >> 4;
                     const float logit = kq_ == 0 ? c[0] : (kq_ == 1 ? c[1] : c[2]);
@@ -843,7 +854,48 @@ __global__ void __launch_bounds__(P::WAVES * 64) render_kernel(const RenderArgs 
                 // (broadcast ds_read_b128), no per-entry LDS round trip
                 // (an entry of another ray adds m * v = +0: the weighted colours are finite and the sums non-negative, so `x + 0` is
                 // `x` to the bit -- one select + three FMAs per entry instead of three selects + three adds)
-                {
+                if constexpr (C3) {
+                    // No v_cmpx, one add per entry.  A ray of a tile of <= 8 rays has at least eight lanes; its three colour sums live in `cr` of its seg-0, 1, 2
+                    // lanes (red, green, blue: `step` lanes apart, step = M of split_chain, 1 in the whole-row forms) and move to the seg-0 lane at the tile's end.
+                    // An entry's owner lane is wave-uniform: the sixteen ids are packed four to a dword inside their quad of lanes (two DPP moves), four
+                    // v_readlane bring them to an SGPR, and per entry the scalar unit makes EXEC = (1 | 1 << step | 1 << 2 step) << owner lane (s_bfe, s_lshl_b64)
+                    // for ONE v_add_f32: each of the three lanes adds ITS channel of the entry, read from the list with the lane's own address (four
+                    // ds_read_b128 instead of sixteen).  Per channel the adds and their order are those of the v_cmpx form (`cr += v` in queue order): its bits.
+                    // Entries beyond nb are steered to lane 63, which is no ray's seg-0, 1 or 2 lane in a tile of <= 8 rays (its seg is 63, 31, 15, 7): for
+                    // every sum that is read their mask is empty.
+                    // (Split tiles of 16 / 32 / 64 rays -- the tile_w knob alone asks for them; 32 and 64 have fewer than three lanes per ray -- keep the
+                    // twelve-wave kernel: level3_waves16 in ngf_field.hip.  With the v_cmpx form behind a wave-uniform branch for them, or with a third mask
+                    // pattern for 16 rays, hipcc gives this kernel 36-48 B of scratch per lane and v_readlane in the pass.)
+                    static_assert(BATCH == 16, "four packed dwords of four owner ids");
+                    const int ob = lane < nb ? owner_lane : 63;
+                    const int oq = ob | (__builtin_amdgcn_update_dpp(0, ob, 0xF5, 0xf, 0xf, false) << 8);           // quad_perm:[1,1,3,3]: lanes 0 / 2 of a quad hold ids 0, 1 / 2, 3
+                    const int op = oq | (__builtin_amdgcn_update_dpp(0, oq, 0xAA, 0xf, 0xf, false) << 16);          // quad_perm:[2,2,2,2]: lane 0 of a quad holds its four ids
+                    const unsigned long long pat = ts == 3 ? 0x15ull : 0x7ull;          // step 2 (8-ray tiles: M = 2) | step 1; a scalar select per pass, held in an SGPR pair
+                    const f32x4 *vp = reinterpret_cast<const f32x4 *>(res + (1 + (seg < 2 ? seg : 2)) * BATCH);
+                    const f32x4 v0 = vp[0], v1 = vp[1], v2 = vp[2], v3 = vp[3];
+                    // (one asm block: nothing of the compiler's may run under the narrowed EXEC.  The pass runs with EXEC all ones -- whole waves, wave-uniform
+                    // control flow: `count`, `i` and the tile are wave-uniform, the waves_active return is per wave -- so EXEC is set back to -1 rather than saved:
+                    // two SGPRs less in a kernel that parks scalars in VGPR lanes.  A later lane-divergent guard around the pass would break this: the DBG
+                    // instantiations, which every test runs, trap when EXEC is not all ones here.  v_readlane ignores EXEC, and one id dword is live at a time)
+                    if constexpr (DBG) {
+                        if (__builtin_amdgcn_read_exec() != ~0ull) __builtin_trap();
+                    }
+                    int ids, sh;
+#define NGF_C3_ENTRY(BYTE, VAL)                                                                                                   \
+                    "s_bfe_u32 %[sh], %[ids], 0x800" BYTE "\n\t"                                                                   \
+                    "s_lshl_b64 exec, %[pat], %[sh]\n\t"                                                                           \
+                    "v_add_f32_e32 %[cr], %[cr], %[" VAL "]\n\t"
+#define NGF_C3_QUAD(LANE, V) "v_readlane_b32 %[ids], %[op], " LANE "\n\t" NGF_C3_ENTRY("00", V "0") NGF_C3_ENTRY("08", V "1") NGF_C3_ENTRY("10", V "2") NGF_C3_ENTRY("18", V "3")
+                    asm volatile(NGF_C3_QUAD("0", "a") NGF_C3_QUAD("4", "b") NGF_C3_QUAD("8", "c") NGF_C3_QUAD("12", "d")
+                                 "s_mov_b64 exec, -1"
+                                 : [cr] "+v"(cr), [ids] "=&s"(ids), [sh] "=&s"(sh)
+                                 : [pat] "s"(pat), [op] "v"(op),
+                                   [a0] "v"(v0[0]), [a1] "v"(v0[1]), [a2] "v"(v0[2]), [a3] "v"(v0[3]), [b0] "v"(v1[0]), [b1] "v"(v1[1]), [b2] "v"(v1[2]), [b3] "v"(v1[3]),
+                                   [c0] "v"(v2[0]), [c1] "v"(v2[1]), [c2] "v"(v2[2]), [c3] "v"(v2[3]), [d0] "v"(v3[0]), [d1] "v"(v3[1]), [d2] "v"(v3[2]), [d3] "v"(v3[3])
+                                 : "scc");
+#undef NGF_C3_QUAD
+#undef NGF_C3_ENTRY
+                } else {
 #pragma unroll
                     for (int q = 0; q < BATCH / 4; ++q) {
                         const f32x4 id = *reinterpret_cast<const f32x4 *>(res + 4 * q);
@@ -852,7 +904,10 @@ __global__ void __launch_bounds__(P::WAVES * 64) render_kernel(const RenderArgs 
                         const f32x4 vb = *reinterpret_cast<const f32x4 *>(res + 3 * BATCH + 4 * q);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-#ifndef NGF_COLLECT_SELECT
+#ifdef NGF_EXP_NO_COLLECT     // TIMING EXPERIMENT (wrong pixels): one unmasked add per entry -- no v_cmpx, no EXEC save / restore, a third of the adds and of the list's reads
+                            cr += vr[e];
+                            (void)id; (void)vg; (void)vb;
+#elif !defined(NGF_COLLECT_SELECT)
                             // the entry's owner lane alone adds it: v_cmpx narrows EXEC to that lane, three v_add_f32 run under it, EXEC comes back
                             // (4 VALU instructions per entry; written in C++ -- `if (id == lane) cr += v` -- hipcc if-converts it into three adds +
                             // three selects, and the select + FMA form below is a compare, a select, a packed FMA, an FMA and two moves).  Same sums:
@@ -887,6 +942,12 @@ __global__ void __launch_bounds__(P::WAVES * 64) render_kernel(const RenderArgs 
             } else {
                 break;
             }
+        }
+        if constexpr (SPLIT && collect3<P>::value) {
+            // COLLECT3: the green and blue sums come home from the ray's seg-1 and seg-2 lanes, once per tile (all lanes take part in the permutation)
+            const int step = ts == 3 ? 2 : 1;
+            const float g_ = __shfl(cr, lane + step), b_ = __shfl(cr, lane + 2 * step);
+            cg = g_; cb = b_;
         }
         if (live && seg == 0) {
             // compositing tail (FieldBase.py:296-306)
