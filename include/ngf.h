@@ -520,6 +520,39 @@ int ngf_uv_train_backward(ngf_uv_trainer *t, int64_t ticket, const float *d_colo
 int ngf_uv_train_get_grads(ngf_uv_trainer *t, float *const out[NGF_UV_TRAIN_PARAMS], void *hip_stream);
 /* after writing to a parameter's memory: kept for the trainers' common contract; the UV trainer packs nothing and reads the weights in place */
 int ngf_uv_train_params_changed(ngf_uv_trainer *t);
+/* test aid: ONE layer-sized GEMM of the trainer on caller-owned DEVICE buffers, through the launch code the trainer's layers go through (strides,
+ * grid sizes and the chunk count are the trainer's own), so that a test can compare it with fp64 at the row counts a batch never pins down.
+ * The layer is W [out, in]; `rows` sizes the launch, and with rows_dev set only min(rows, *rows_dev) rows are computed (the in-cube count).
+ *   FORWARD  z [rows, out | ld_z] = act(x [rows, in | ld_x] . W^T + b)
+ *   DX       dx [rows, n_dx | ld_dx] = (z . W[:, :n_dx] + add [rows, n_dx | ld_add] (NULL = none)) x act'(x) (act 0: no mask; x is the layer's
+ *            input, the post-activation output of the producer); z holds dZ
+ *   DW       gw [out, in], gb [out] = dZ^T . x and the column sums of dZ (z holds dZ), over ceil(rows / 1024) chunks of 1024 rows written to
+ *            part [chunks][out, in] and partb [chunks][out] (part_elems / partb_elems floats: the call refuses fewer) and summed in chunk order
+ * size = sizeof(ngf_uvt_gemm_args) as the caller sees it.  Asynchronous on hip_stream. */
+#define NGF_UVT_GEMM_FORWARD 0
+#define NGF_UVT_GEMM_DX 1
+#define NGF_UVT_GEMM_DW 2
+typedef struct ngf_uvt_gemm_args {
+    int32_t size, form;
+    int32_t in, out;
+    int32_t act;                    /* 0 none, 1 ReLU, 2 LeakyReLU(0.2): FORWARD the layer's own, DX the producer's (applied through x) */
+    int32_t n_dx;
+    int64_t rows;
+    const int32_t *rows_dev;        /* DEVICE, or NULL */
+    const float *x;
+    int64_t ld_x;
+    const float *w, *b;
+    float *z;
+    int64_t ld_z;
+    float *dx;
+    int64_t ld_dx;
+    const float *add;
+    int64_t ld_add;
+    float *part, *partb;
+    int64_t part_elems, partb_elems;
+    float *gw, *gb;
+} ngf_uvt_gemm_args;
+int ngf_debug_uvt_gemm(const ngf_uvt_gemm_args *args, void *hip_stream);
 
 /* test hook: the queue-position -> tile map of ngf_field_render_image evaluated on the host for `count` positions (RenderArgs::ord_*: ord_n positions
  * re-ordered, tpr tiles per image row, blocks of bw tiles x bh rows) */

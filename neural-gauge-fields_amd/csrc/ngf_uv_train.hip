@@ -75,18 +75,94 @@ int launch_gemm(const UvtGemm &G, unsigned gx, unsigned gy, unsigned gz, hipStre
     return NGF_OK;
 }
 
+// One Linear as the launch code sees it: caller-owned pointers and leading dimensions.  fwd_layer / bwd_layer fill it from the trainer's buffers,
+// ngf_debug_uvt_gemm from its arguments: strides, grid sizes and the chunk count are computed here, once, for both.
+struct LayerView {
+    int in = 0, out = 0, act = kNone;        // W is [out, in]; the layer's own activation
+    const float *w = nullptr, *b = nullptr;
+    const float *x = nullptr;                // the layer's input [rows, in] (post-activation output of the producer, or an encoding)
+    int64_t ld_x = 0;
+    float *z = nullptr;                      // forward: the output [rows, out]
+    const float *dz = nullptr;               // backward: the pre-activation gradient [rows, out]
+    int64_t ld_z = 0;
+    int64_t rows = 0;                        // static row count (sizes the launch)
+    const int32_t *rows_dev = nullptr;       // rows on the device (the in-cube count): min(rows, *rows_dev) are computed
+    float *dx = nullptr;                     // d input, first n_dx columns
+    int64_t ld_dx = 0;
+    int n_dx = 0;
+    const float *add = nullptr;              // + a second gradient before the mask
+    int64_t ld_add = 0;
+    int act_prev = kNone;                    // x act'(x) of the producing layer (kNone: no mask)
+    float *part = nullptr, *partb = nullptr; // split-K partials [nz][out, in] and [nz][out]
+    float *gw = nullptr, *gb = nullptr;      // the reduced gradients
+};
+
+int view_nz(const LayerView &v) { return (int)((v.rows + kUvtChunk - 1) / kUvtChunk); }
+
+// Z = act(X W^T + b)
+int fwd_view(const LayerView &v, hipStream_t st)
+{
+    UvtGemm G{};
+    G.A = v.x; G.sam = v.ld_x; G.sak = 1;
+    G.B = v.w; G.sbk = 1; G.sbn = v.in;
+    G.C = v.z; G.ldc = v.ld_z;
+    G.bias = v.b; G.act = v.act;
+    G.Mdev = v.rows_dev;
+    G.M = (int32_t)v.rows; G.N = v.out; G.K = v.in;
+    return launch_gemm(G, blocks(v.rows, 64), blocks(v.out, 64), 1, st);
+}
+
+// dW, db = dZ^T X over 1024-row chunks -> part / partb, summed in chunk order -> gw, gb
+int bwd_weights_view(const LayerView &v, hipStream_t st)
+{
+    const int nz = view_nz(v);
+    UvtGemm G{};
+    G.A = v.dz; G.sam = 1; G.sak = v.ld_z;
+    G.B = v.x; G.sbk = v.ld_x; G.sbn = 1;
+    G.C = v.part; G.ldc = v.in; G.czs = (int64_t)v.out * v.in;
+    G.Mdev = v.rows_dev;
+    G.M = v.out; G.N = v.in; G.K = (int32_t)v.rows;
+    G.split = 1; G.chunk = kUvtChunk; G.partb = v.partb;
+    int rc = launch_gemm(G, blocks(v.out, 64), blocks(v.in, 64), (unsigned)std::max(1, nz), st);
+    if (rc) return rc;
+    const int64_t nk = (int64_t)v.out * v.in;
+    hipLaunchKernelGGL(uvt_reduce_kernel, dim3(blocks(nk)), dim3(256), 0, st, (const float *)v.part, (const float *)v.partb, nk, v.out, (int)v.rows,
+                       v.rows_dev, v.gw, v.gb);
+    HIP_TRY(hipGetLastError());
+    return NGF_OK;
+}
+
+// dX (first n_dx input columns) = (dZ W + add) x act_prev'(x)
+int bwd_input_view(const LayerView &v, hipStream_t st)
+{
+    UvtGemm G{};
+    G.A = v.dz; G.sam = v.ld_z; G.sak = 1;
+    G.B = v.w; G.sbk = v.in; G.sbn = 1;
+    G.C = v.dx; G.ldc = v.ld_dx;
+    G.add = v.add; G.ldadd = v.ld_add;
+    if (v.act_prev != kNone) { G.aux = v.x; G.ldaux = v.ld_x; G.act = v.act_prev; }
+    G.Mdev = v.rows_dev;
+    G.M = (int32_t)v.rows; G.N = v.n_dx; G.K = v.out;
+    return launch_gemm(G, blocks(v.rows, 64), blocks(v.n_dx, 64), 1, st);
+}
+
+LayerView layer_view(const ngf_uv_trainer *t, int l, int64_t rows, const int32_t *rows_dev)
+{
+    const LayerShape &s = t->shape[l];
+    LayerView v;
+    v.in = s.in; v.out = s.out; v.act = s.act;
+    v.w = t->desc.w[l]; v.b = t->desc.b[l];
+    v.x = t->in[l]; v.ld_x = t->in_ld[l];
+    v.rows = rows; v.rows_dev = rows_dev;
+    return v;
+}
+
 // forward of layer l over `rows` rows (the in-cube count on the device when rows_dev is set)
 int fwd_layer(ngf_uv_trainer *t, int l, int64_t rows, const int32_t *rows_dev, hipStream_t st)
 {
-    const LayerShape &s = t->shape[l];
-    UvtGemm G{};
-    G.A = t->in[l]; G.sam = t->in_ld[l]; G.sak = 1;
-    G.B = t->desc.w[l]; G.sbk = 1; G.sbn = s.in;
-    G.C = t->out[l]; G.ldc = t->out_ld[l];
-    G.bias = t->desc.b[l]; G.act = s.act;
-    G.Mdev = rows_dev;
-    G.M = (int32_t)rows; G.N = s.out; G.K = s.in;
-    return launch_gemm(G, blocks(rows, 64), blocks(s.out, 64), 1, st);
+    LayerView v = layer_view(t, l, rows, rows_dev);
+    v.z = t->out[l]; v.ld_z = t->out_ld[l];
+    return fwd_view(v, st);
 }
 
 // backward of layer l from dZ (its pre-activation gradient, [rows, out] at ld): dW, db -> the gradient slots; dX (first n_dx input columns) ->
@@ -94,33 +170,15 @@ int fwd_layer(ngf_uv_trainer *t, int l, int64_t rows, const int32_t *rows_dev, h
 int bwd_layer(ngf_uv_trainer *t, int l, const float *dz, int64_t ldz, int64_t rows, const int32_t *rows_dev, float *dx, int64_t ld_dx, int n_dx,
               const float *add, int64_t ld_add, int act_prev, hipStream_t st)
 {
-    const LayerShape &s = t->shape[l];
-    const int nz = (int)((rows + kUvtChunk - 1) / kUvtChunk);
-    {
-        UvtGemm G{};
-        G.A = dz; G.sam = 1; G.sak = ldz;
-        G.B = t->in[l]; G.sbk = t->in_ld[l]; G.sbn = 1;
-        G.C = t->part; G.ldc = s.in; G.czs = (int64_t)s.out * s.in;
-        G.Mdev = rows_dev;
-        G.M = s.out; G.N = s.in; G.K = (int32_t)rows;
-        G.split = 1; G.chunk = kUvtChunk; G.partb = t->partb;
-        int rc = launch_gemm(G, blocks(s.out, 64), blocks(s.in, 64), (unsigned)std::max(1, nz), st);
-        if (rc) return rc;
-        const int64_t nk = (int64_t)s.out * s.in;
-        hipLaunchKernelGGL(uvt_reduce_kernel, dim3(blocks(nk)), dim3(256), 0, st, (const float *)t->part, (const float *)t->partb, nk, s.out, (int)rows,
-                           rows_dev, t->grads + t->grad_off[2 * l], t->grads + t->grad_off[2 * l + 1]);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!dx) return NGF_OK;
-    UvtGemm G{};
-    G.A = dz; G.sam = ldz; G.sak = 1;
-    G.B = t->desc.w[l]; G.sbk = s.in; G.sbn = 1;
-    G.C = dx; G.ldc = ld_dx;
-    G.add = add; G.ldadd = ld_add;
-    if (act_prev != kNone) { G.aux = t->in[l]; G.ldaux = t->in_ld[l]; G.act = act_prev; }
-    G.Mdev = rows_dev;
-    G.M = (int32_t)rows; G.N = n_dx; G.K = s.out;
-    return launch_gemm(G, blocks(rows, 64), blocks(n_dx, 64), 1, st);
+    LayerView v = layer_view(t, l, rows, rows_dev);
+    v.dz = dz; v.ld_z = ldz;
+    v.part = t->part; v.partb = t->partb;
+    v.gw = t->grads + t->grad_off[2 * l]; v.gb = t->grads + t->grad_off[2 * l + 1];
+    int rc = bwd_weights_view(v, st);
+    if (rc || !dx) return rc;
+    v.dx = dx; v.ld_dx = ld_dx; v.n_dx = n_dx;
+    v.add = add; v.ld_add = ld_add; v.act_prev = act_prev;
+    return bwd_input_view(v, st);
 }
 
 }  // namespace
@@ -335,6 +393,50 @@ int ngf_uv_train_get_grads(ngf_uv_trainer *t, float *const out[NGF_UV_TRAIN_PARA
         HIP_TRY(hipMemcpyAsync(out[k], t->grads + t->grad_off[k], (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return NGF_OK;
+}
+
+// test aid (include/ngf.h): one layer-sized call on caller-owned buffers through the trainer's own launch code
+int ngf_debug_uvt_gemm(const ngf_uvt_gemm_args *a, void *hip_stream)
+{
+    if (!a) return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: null argument");
+    if (a->size != (int32_t)sizeof(ngf_uvt_gemm_args)) return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: ngf_uvt_gemm_args layout mismatch");
+    if (a->in <= 0 || a->out <= 0 || a->rows <= 0 || a->rows >= ((int64_t)1 << 31) / 296)
+        return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: in, out and rows must be > 0 (rows x 296 below 2^31)");
+    if (a->act < kNone || a->act > kLeaky) return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: unknown activation %d", a->act);
+    if (!a->z || a->ld_z < a->out) return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: z is null or ld_z < out");
+    LayerView v;
+    v.in = a->in; v.out = a->out;
+    v.w = a->w; v.b = a->b;
+    v.x = a->x; v.ld_x = a->ld_x;
+    v.rows = a->rows; v.rows_dev = a->rows_dev;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (a->form == NGF_UVT_GEMM_FORWARD) {
+        if (!a->x || !a->w || !a->b || a->ld_x < a->in) return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: forward needs x (ld_x >= in), w and b");
+        v.act = a->act;
+        v.z = a->z; v.ld_z = a->ld_z;
+        return fwd_view(v, st);
+    }
+    v.dz = a->z; v.ld_z = a->ld_z;
+    if (a->form == NGF_UVT_GEMM_DX) {
+        if (!a->w || !a->dx || a->n_dx <= 0 || a->n_dx > a->in || a->ld_dx < a->n_dx)
+            return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: dX needs w, dx and 0 < n_dx <= in, ld_dx");
+        if (a->add && a->ld_add < a->n_dx) return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: ld_add < n_dx");
+        if (a->act != kNone && (!a->x || a->ld_x < a->n_dx)) return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: the mask needs x (ld_x >= n_dx)");
+        v.dx = a->dx; v.ld_dx = a->ld_dx; v.n_dx = a->n_dx;
+        v.add = a->add; v.ld_add = a->ld_add; v.act_prev = a->act;
+        return bwd_input_view(v, st);
+    }
+    if (a->form == NGF_UVT_GEMM_DW) {
+        if (!a->x || a->ld_x < a->in || !a->part || !a->partb || !a->gw || !a->gb)
+            return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: dW needs x (ld_x >= in), part, partb, gw and gb");
+        const int64_t nz = view_nz(v);
+        if (a->part_elems < nz * a->out * a->in || a->partb_elems < nz * a->out)
+            return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: part / partb hold fewer than %lld chunks", (long long)nz);
+        v.part = a->part; v.partb = a->partb;
+        v.gw = a->gw; v.gb = a->gb;
+        return bwd_weights_view(v, st);
+    }
+    return fail(NGF_E_ARG, "ngf_debug_uvt_gemm: unknown form %d", a->form);
 }
 
 }  // extern "C"

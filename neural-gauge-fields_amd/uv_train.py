@@ -21,9 +21,39 @@ class UvTrainDesc(C.Structure):
                 ("max_rays", C.c_int64), ("max_samples", C.c_int32), ("pad_", C.c_int32)]
 
 
+class UvtGemmArgs(C.Structure):
+    """ngf_uvt_gemm_args (include/ngf.h): one layer-sized GEMM of the trainer on caller-owned buffers, a test aid."""
+    _fields_ = [("size", C.c_int32), ("form", C.c_int32), ("in_", C.c_int32), ("out", C.c_int32), ("act", C.c_int32), ("n_dx", C.c_int32),
+                ("rows", C.c_int64), ("rows_dev", C.c_void_p), ("x", C.c_void_p), ("ld_x", C.c_int64), ("w", C.c_void_p), ("b", C.c_void_p),
+                ("z", C.c_void_p), ("ld_z", C.c_int64), ("dx", C.c_void_p), ("ld_dx", C.c_int64), ("add", C.c_void_p), ("ld_add", C.c_int64),
+                ("part", C.c_void_p), ("partb", C.c_void_p), ("part_elems", C.c_int64), ("partb_elems", C.c_int64),
+                ("gw", C.c_void_p), ("gb", C.c_void_p)]
+
+
+GEMM_FORWARD, GEMM_DX, GEMM_DW = 0, 1, 2
+
+
+def debug_gemm(form, stream=None, **kw):
+    """ngf_debug_uvt_gemm: keyword = field of UvtGemmArgs; a torch tensor is passed as its data pointer (``part`` / ``partb`` also set
+    their element counts).  Returns the library's return code: 0, or 1 with ngf_last_error() set."""
+    L = _lib.lib()
+    _bind(L)
+    a = UvtGemmArgs()
+    a.size, a.form = C.sizeof(UvtGemmArgs), int(form)
+    for k, v in kw.items():
+        if isinstance(v, torch.Tensor):
+            if k in ("part", "partb"):
+                setattr(a, k + "_elems", v.numel())
+            v = v.data_ptr()
+        setattr(a, k, v)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    return L.ngf_debug_uvt_gemm(C.byref(a), C.c_void_p(st))
+
+
 def _bind(L):
     if getattr(L, "_ngf_uv_train_bound", False):
         return
+    L.ngf_debug_uvt_gemm.argtypes = [C.POINTER(UvtGemmArgs), C.c_void_p]
     L.ngf_uv_trainer_create.argtypes = [C.POINTER(UvTrainDesc), C.POINTER(C.c_void_p), C.c_void_p]
     L.ngf_uv_trainer_destroy.argtypes = [C.c_void_p]
     L.ngf_uv_trainer_bytes.argtypes = [C.c_void_p]

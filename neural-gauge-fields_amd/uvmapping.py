@@ -386,6 +386,11 @@ class NeuTex(nn.Module):
             self._uv_engine = UvGrad(self, max(nrays, old[0]), max(S, old[1]))
         return self._uv_engine
 
+    @property
+    def grad_engine(self):
+        """The training engine (uv_train.UvGrad: max_rays, max_samples, bytes) of the last differentiable forward, or None."""
+        return self._uv_engine
+
     def release_grad_engine(self):
         """Free the training engine's per-sample buffers (the next differentiable forward builds a new one)."""
         if self._uv_engine is not None:

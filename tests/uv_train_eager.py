@@ -4,6 +4,7 @@ compute_loss (model.py:300-349).  The reference itself cannot be imported where 
 
 ``torch.rand`` of cube_ray_generation is replaced by ``U`` and the template's random points by ``template_points``.  The inverse
 mapping runs the inverse network on the flattened uv (the reference's ``uv.view(input_shape, -1, D)`` raises in torch)."""
+import functools
 import zlib
 
 import numpy as np
@@ -46,11 +47,13 @@ def inverse_network(inv, x):
     return inv.last_linear(x)
 
 
-def forward(net, campos, raydir, bg, U, template_points):
-    """The training dict of model.py:27-59 (points_inverse computed eagerly)."""
+def forward(net, campos, raydir, bg, U, template_points, extras=False):
+    """The training dict of model.py:27-59 (points_inverse computed eagerly).  extras: also "valid", "raw_density" and "color1_pre" (the
+    softplus arguments of every sample) and "color_unclamped" (the tone-mapped colour before clamp_(0, 1))."""
     S = U.shape[-1]
     pos, seg, valid = cube_ray_generation(campos, raydir, S, U)
-    density = F.softplus(net.net_geometry_decoder.block(torch.cat([pos, positional_encoding(pos, 10)], dim=-1))[..., 0])
+    raw = net.net_geometry_decoder.block(torch.cat([pos, positional_encoding(pos, 10)], dim=-1))[..., 0]
+    density = F.softplus(raw)
     inv = net.inverse_gauge.inverse_network
     pts3 = inverse_network(inv, template_points.unsqueeze(0)).unsqueeze(1)
     points = pts3.view(pts3.shape[0], -1, pts3.shape[-1]).permute(0, 2, 1)
@@ -63,7 +66,8 @@ def forward(net, campos, raydir, bg, U, template_points):
     uv = torch.tanh(q) if q.shape[-1] == 2 else F.normalize(q, dim=-1)
     t = net.net_texture
     h = t.block1(torch.cat([uv, positional_encoding(uv, 10)], dim=-1))
-    c1 = F.softplus(t.color1(h))
+    c1_pre = t.color1(h)
+    c1 = F.softplus(c1_pre)
     vd = raydir[:, :, None, :].expand(h.shape[:-1] + (3,))
     c2 = t.block2(torch.cat([h, vd, positional_encoding(vd, 6)], dim=-1))
     radiance = (c1 + c2).clamp(min=0)
@@ -76,10 +80,14 @@ def forward(net, campos, raydir, bg, U, template_points):
     color = torch.sum(radiance * w[..., None], dim=-2)
     if bg is not None:
         color = color + bg[:, None, :] * bgT[:, :, None]
-    color = torch.pow(color + 1e-5, 1 / 2.2).clamp_(0, 1)
+    unclamped = torch.pow(color + 1e-5, 1 / 2.2)
+    color = unclamped.clone().clamp_(0, 1)
     pinv = inverse_network(inv, uv.reshape(-1, uv.shape[-1])).view(uv.shape[:-1] + (3,))
-    return {"color": color, "transmittance": bgT, "points": points, "points_original": pos, "points_inverse": pinv,
-            "points_inverse_weights": w, "uv": uv}
+    out = {"color": color, "transmittance": bgT, "points": points, "points_original": pos, "points_inverse": pinv,
+           "points_inverse_weights": w, "uv": uv}
+    if extras:
+        out.update(valid=valid.bool(), raw_density=raw.detach(), color1_pre=c1_pre.detach(), color_unclamped=unclamped.detach())
+    return out
 
 
 def compute_loss(out, gt_image, gt_trans, weights=(1.0, 1.0, 1.0, 0.0)):
@@ -172,3 +180,118 @@ def fixture_idx(g):
     names = [str(n) for n in g["names"]]
     ends = np.cumsum(g["idx_len"])
     return {k: g["idx"][e - n:e] for k, e, n in zip(names, ends, g["idx_len"])}
+
+
+# ---- batches at the edges (tests/test_gpu_uv_train_edges.py, tests/test_uv_train_edges_cpu.py) -------------------------------------------------
+EDGE_SEEDS = (311, 312, 313)                         # every case runs on three seeds (model and batch)
+EDGE_V, EDGE_V_S = (0, 1, 17, 1023, 1024, 1025, 2049), 23
+EDGE_RAYS, EDGE_RAYS_S = (1, 257, 1025, 2051), 5
+EDGE_CAMS = (3, 343)                                 # cameras x rays per camera, at EDGE_RAYS_S samples
+POOL_STRIDE = 97          # every 97th ray of the 600 x 800 DTU frame: 4949 rays
+FACE_MARGIN = 1e-5        # a pool ray is used only if each of its samples stays this far from every cube face
+
+
+def in_cube_counts(campos, raydir, U):
+    """fp64 in-cube count per ray and the smallest distance of any of its samples to a cube face (campos [3], raydir [R,3], U [R,S])."""
+    t = lambda a: torch.from_numpy(np.asarray(a, np.float64))          # noqa: E731
+    pos, _, valid = cube_ray_generation(t(campos)[None], t(raydir)[None], U.shape[-1], t(U)[None])
+    margin = (pos.abs() - 1.0).abs().amin(dim=(-1, -2))[0].numpy()
+    return valid[0].sum(-1).numpy().astype(np.int64), margin
+
+
+@functools.lru_cache(maxsize=32)
+def _pool(seed, S, c):
+    """camera c of a seed: its position, the pool's directions and jitter rows, their fp64 counts and margins, the usable rays in seeded order"""
+    campos, dirs = synth.dtu_rays(600, 800)
+    pool = dirs[::POOL_STRIDE]
+    pool = (pool / np.linalg.norm(pool, axis=1, keepdims=True)).astype(np.float32)
+    n = pool.shape[0]
+    cp = (np.asarray(campos, np.float32) * np.float32(1.0 + 0.05 * c)).astype(np.float32)
+    Up = synth.hash_uniform(seed + c, 601, (n, S))
+    cnt, mg = in_cube_counts(cp, pool, Up)
+    order = np.argsort(synth.hash_uniform(seed + c, 600, (n,)), kind="stable")
+    return cp, pool, Up, cnt, mg, order[mg[order] >= FACE_MARGIN]
+
+
+def edge_batch(seed, primitive_type, S, V=None, R=None, n_cams=1, misses=3, P=64):
+    """A batch like ``batch`` whose rays come from the pool by their fp64 in-cube counts at S samples, every sample at least FACE_MARGIN
+    away from the faces (so fp32 and fp64 agree on which samples are in the cube).  V: one camera, the fewest rays whose counts add up to
+    exactly V in-cube samples, then `misses` rays that miss, then one more if the ray count is a multiple of 16 (rays x S stays ragged
+    for odd S).  R: R rays per camera in a seeded order, whatever their counts; camera c stands at campos (1 + 0.05 c).
+    Adds "counts" [n_cams, R] and "margin" (the smallest face distance of the batch) to the dict of ``batch``."""
+    cams, rds, Us, cnts, margin = [], [], [], [], np.inf
+    for c in range(n_cams):
+        cp, pool, Up, cnt, mg, order = _pool(seed, S, c)
+        if V is not None:
+            assert n_cams == 1
+            pick, left = [], int(V)
+            for j in order[np.argsort(-cnt[order], kind="stable")]:
+                if 0 < cnt[j] <= left:
+                    pick.append(j)
+                    left -= int(cnt[j])
+            assert left == 0, "the pool cannot reach this count"
+            miss = [j for j in order if cnt[j] == 0]
+            pick += miss[:misses + (1 if (len(pick) + misses) % 16 == 0 else 0)]
+            pick = np.asarray(pick, np.int64)
+        else:
+            pick = order[:R]
+            assert len(pick) == R
+        cams.append(cp)
+        rds.append(pool[pick])
+        Us.append(Up[pick])
+        cnts.append(cnt[pick])
+        margin = min(margin, float(mg[pick].min()))
+    Rn = rds[0].shape[0]
+    if primitive_type == "square":
+        tp = synth.hash_uniform(seed, 602, (P, 2)) * np.float32(2) - np.float32(1)
+    else:
+        q = synth.hash_normal(seed, 602, (P, 3)) * np.float32(2) - np.float32(1)
+        tp = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
+    return {"campos": np.stack(cams).astype(np.float32), "raydir": np.stack(rds).astype(np.float32), "U": np.stack(Us).astype(np.float32),
+            "template": tp.astype(np.float32), "gt_image": synth.hash_uniform(seed, 603, (n_cams, Rn, 3)),
+            "gt_trans": synth.hash_uniform(seed, 604, (n_cams, Rn)), "counts": np.stack(cnts), "margin": margin}
+
+
+DENSITY_BIAS, COLOR1_BIAS = "net_geometry_decoder.block.22.bias", "net_texture.color1.bias"
+
+
+def softplus_case(seed, which, R=24, S=24):
+    """A square model and batch whose softplus arguments straddle torch's threshold of 20 (the seeded ones stay below 2.2, so that branch of
+    uvt_softplus / uvt_dsoftplus never runs otherwise).  which = "density": the density bias is shifted so that 20 falls into the widest gap between the raw densities
+    of the in-cube samples around their median.  which = "color1": the colour1 bias likewise, and the density bias DOWN to a median raw density of -4.5, so
+    that the pixels stay below the tone map's clamp and d color1 is not zero.  The shifts come from the fp64 restatement on the CPU.
+    -> (params, batch, stats) with stats = the fp64 shares the tests assert: "above" (share of the in-cube arguments above 20), "gap" (the
+    smallest |argument - 20|: fp32 and fp64 must take the same branch) and "unclamped" (share of the colour values below the clamp)."""
+    params = model_params(seed, "square")
+    b = batch(seed, "square", R=R, S=S)
+    t = lambda k: torch.from_numpy(b[k]).double()          # noqa: E731
+
+    def look(p):
+        net = make_net(p, "square", S, "cpu", torch.float64)
+        with torch.no_grad():
+            o = forward(net, t("campos"), t("raydir"), None, t("U"), t("template"), extras=True)
+        v = o["valid"]
+        return o["raw_density"][v], o["color1_pre"][v], o["color_unclamped"]
+
+    def shifted(p, name, by):
+        q = dict(p)
+        q[name] = (np.asarray(p[name], np.float64) + by).astype(np.float32)
+        return q
+
+    def split_point(a):
+        """the middle of the widest gap between neighbouring values from the 40th to the 60th percentile: no argument lands near 20"""
+        a = np.sort(a.reshape(-1).numpy())
+        a = a[int(0.4 * a.size):int(0.6 * a.size) + 1]
+        i = int(np.argmax(np.diff(a)))
+        return 0.5 * float(a[i] + a[i + 1])
+
+    raw, c1, _ = look(params)
+    if which == "density":
+        params = shifted(params, DENSITY_BIAS, 20.0 - split_point(raw))
+    else:
+        params = shifted(shifted(params, COLOR1_BIAS, 20.0 - split_point(c1)), DENSITY_BIAS, -4.5 - float(raw.median()))
+    raw, c1, unclamped = look(params)
+    arg = raw if which == "density" else c1
+    stats = {"above": float((arg > 20).double().mean()), "gap": float((arg - 20).abs().min()), "unclamped": float((unclamped < 1).double().mean()),
+             "in_cube": int(raw.numel())}
+    return params, b, stats
