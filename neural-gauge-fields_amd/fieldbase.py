@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, geometry
+from . import _engine, _lib, geometry
 
 
 class AlphaGridMask(torch.nn.Module):
@@ -158,15 +158,7 @@ class Base(torch.nn.Module):
         or the parameter tensors were re-allocated (up_sampling / shrink / load).  One key computation per call (the loop of main.py:272-296 pays
         it once per iteration: ``_render_train`` takes the parameter list from the engine, the backward checks the engine's identity)."""
         from . import train
-        eng = getattr(self, '_grad_engine', None)
-        params = train._train_params(self)
-        if eng is not None and eng._h is not None and eng.fits(n, S, params):
-            return eng
-        if eng is not None:
-            eng.release()
-        eng = train.RenderGrad(self, max(int(n), getattr(eng, 'max_rays', 0)), max(int(S), getattr(eng, 'max_samples', 0)))
-        self._grad_engine = eng
-        return eng
+        return _engine.grad_engine(self, '_grad_engine', train.RenderGrad, train._train_params(self), n, S)
 
     def _wants_grad(self, is_train):
         if not (is_train and torch.is_grad_enabled()):
@@ -177,37 +169,14 @@ class Base(torch.nn.Module):
         return any(p.requires_grad for p in self.parameters())
 
     def _render_train(self, rays_chunk, white_bg, N_samples, gauge_on, jitter=None, coin=None):
-        """``forward(is_train=True)`` with gradients: the same random draws as ``_render`` (jitter: torch.rand_like of sample_ray,
-        FieldBase.py:128-130; background coin: FieldBase.py:299), then one torch.autograd.Function over the fifteen parameters.  The
+        """``forward(is_train=True)`` with gradients (``_engine.render_train``): one torch.autograd.Function over the fifteen parameters.  The
         reference's loop works unchanged on the result: ``loss(out['rgb_map'], ...) + w * field.density_L1()``, ``.backward()``,
-        ``torch.optim.Adam(field.get_optparam_groups(...)).step()`` (TriPlane/main.py:272-296)."""
+        ``torch.optim.Adam(field.get_optparam_groups(...)).step()`` (TriPlane/main.py:272-296).
+        Memory: the engine keeps per-(ray, sample) buffers (136 B per pair) and activation rows for a third of the pairs (2.4 KB each) --
+        3.4 GiB at the reference's 4096 x 884 batch; the default ``grad_max_pairs`` of 2^24 is 4.6 batches of that size, ~16 GiB."""
         from . import train
-        dev = torch.device(self.device)
-        rays = rays_chunk.detach().to(device=dev, dtype=torch.float32).contiguous()
-        if rays.dim() != 2 or rays.shape[1] != 6:
-            raise ValueError(f"rays_chunk must be [n,6], got {tuple(rays.shape)}")
-        n = rays.shape[0]
-        if n == 0:
-            raise ValueError("a differentiable forward needs at least one ray")
-        S = int(N_samples) if N_samples > 0 else int(self.nSamples)
-        jitter = torch.rand((n,), device=dev) if jitter is None else jitter.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
-        white = bool(white_bg or ((torch.rand((1,)) if coin is None else torch.tensor([float(coin)])) < 0.5))
-        # Memory of a differentiable forward (ADVICE r5): the engine keeps per-(ray, sample) buffers (136 B per pair) and activation rows for a third
-        # of the pairs (2.4 KB each) -- 3.4 GiB at the reference's 4096 x 884 batch, growing with n x S.  A call beyond ``grad_max_pairs`` pairs
-        # (default 2^24 = 4.6 batches of that size, ~16 GiB) is cut into ray chunks, one autograd node each: the engine holds ONE chunk, so the
-        # backward renders every chunk but the last again (what two forwards before one backward always did) -- bounded memory for twice the forward.
-        cap = max(int(getattr(self, 'grad_max_pairs', 1 << 24)), S)
-        per = max(1, cap // S)
-        if n > per:
-            outs = []
-            for a in range(0, n, per):
-                r, j = rays[a:a + per], jitter[a:a + per]
-                eng = self._render_grad_engine(r.shape[0], S)
-                outs.append(train._TrainRender.apply(self, eng, r, j, S, white, bool(gauge_on), *eng.params))
-            return {'rgb_map': torch.cat([o[0] for o in outs], 0), 'depth_map': torch.cat([o[1] for o in outs], 0)}
-        eng = self._render_grad_engine(n, S)
-        rgb, depth = train._TrainRender.apply(self, eng, rays, jitter, S, white, bool(gauge_on), *eng.params)
-        return {'rgb_map': rgb, 'depth_map': depth}
+        return _engine.render_train(self, rays_chunk, white_bg, N_samples, gauge_on, jitter, coin, 1 << 24, self._render_grad_engine,
+                                    train._TrainRender)
 
     def invalidate(self):
         """Force the packed device image to be rebuilt at the next call.  The handle is rebuilt automatically when a parameter

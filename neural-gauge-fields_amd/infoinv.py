@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _engine, _lib
 from .fieldbase import AlphaGridMask, Base, density_decoder, renderer, rgb_decoder  # noqa: F401
 from .triplane import _DensityL1
 
@@ -58,51 +58,19 @@ class TriPlane(Base):
         """The device trainer behind a differentiable forward (ngf_amd.infoinv_train.InfoInvGrad); rebuilt when the batch outgrows it or a
         parameter tensor / the alpha mask / the geometry was replaced."""
         from . import infoinv_train
-        eng = getattr(self, '_ii_engine', None)
-        params = infoinv_train.train_params(self)
-        if eng is not None and eng._h is not None and eng.fits(n, S, params):
-            return eng
-        if eng is not None:
-            eng.release()
-            self._ii_engine = None
-        eng = infoinv_train.InfoInvGrad(self, max(int(n), getattr(eng, 'max_rays', 0)), max(int(S), getattr(eng, 'max_samples', 0)))
-        self._ii_engine = eng
-        return eng
+        return _engine.grad_engine(self, '_ii_engine', infoinv_train.InfoInvGrad, infoinv_train.train_params(self), n, S)
 
     def release_grad_engine(self):
         """Free the differentiable forward's device buffers (about 3.5 KB per (ray, sample) pair of the largest batch seen, up to ~15 GB at the default
         ``grad_max_pairs``); the next differentiable forward builds the engine again.  A pending backward of an earlier forward re-renders its batch."""
-        eng = getattr(self, '_ii_engine', None)
-        if eng is not None:
-            eng.release()
-            self._ii_engine = None
+        _engine.release_engine(self, '_ii_engine')
 
     def _render_train_infoinv(self, rays_chunk, white_bg, N_samples, infoinv, jitter=None, coin=None):
-        """``forward(is_train=True)`` with gradients: the random draws of ``_render`` (jitter: torch.rand_like of sample_ray, FieldBase.py:128-130;
-        background coin: FieldBase.py:270), then one torch.autograd.Function over the sixteen parameters.  A batch of more than ``grad_max_pairs``
-        (ray, sample) pairs (default 2^22, ~16 GB of per-sample buffers) is cut into ray chunks, one autograd node each: the engine holds one chunk,
-        so the backward renders the other chunks again."""
+        """``forward(is_train=True)`` with gradients (``_engine.render_train``; the background coin: FieldBase.py:270): one torch.autograd.Function
+        over the sixteen parameters per ray chunk of at most ``grad_max_pairs`` (ray, sample) pairs (default 2^22, ~16 GB of per-sample buffers)."""
         from . import infoinv_train
-        dev = torch.device(self.device)
-        rays = rays_chunk.detach().to(device=dev, dtype=torch.float32).contiguous()
-        if rays.dim() != 2 or rays.shape[1] != 6:
-            raise ValueError(f"rays_chunk must be [n,6], got {tuple(rays.shape)}")
-        n = rays.shape[0]
-        if n == 0:
-            raise ValueError("a differentiable forward needs at least one ray")
-        S = int(N_samples) if N_samples > 0 else int(self.nSamples)
-        jitter = torch.rand((n,), device=dev) if jitter is None else jitter.detach().to(device=dev, dtype=torch.float32).reshape(n).contiguous()
-        white = bool(white_bg or ((torch.rand((1,)) if coin is None else torch.tensor([float(coin)])) < 0.5))
-        cap = max(int(getattr(self, 'grad_max_pairs', 1 << 22)), S)
-        per = max(1, cap // S)
-        outs = []
-        for a in range(0, n, per):
-            r, j = rays[a:a + per], jitter[a:a + per]
-            eng = self._infoinv_grad_engine(r.shape[0], S)
-            outs.append(infoinv_train._InfoInvRender.apply(self, eng, r, j, S, white, bool(infoinv), *eng.params))
-        if len(outs) == 1:
-            return {'rgb_map': outs[0][0], 'depth_map': outs[0][1]}
-        return {'rgb_map': torch.cat([o[0] for o in outs], 0), 'depth_map': torch.cat([o[1] for o in outs], 0)}
+        return _engine.render_train(self, rays_chunk, white_bg, N_samples, infoinv, jitter, coin, infoinv_train.MAX_PAIRS,
+                                    self._infoinv_grad_engine, infoinv_train._InfoInvRender)
 
     def forward(self, rays_chunk, white_bg=True, is_train=False, N_samples=-1, infoinv=True, collect_stats=False, out=None, jitter=None, coin=None, row_width=0):
         """InfoInv/models/FieldBase.py:228.  A call that the reference would record for autograd (is_train=True, grad enabled, parameters

@@ -15,8 +15,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import GradEngine, TrainerBase, fill_geometry, on_stream, rays_per_chunk, replay
 
 L1_REG_WEIGHT = 8e-5            # InfoInv/main.py:259
+MAX_PAIRS = 1 << 22             # default of ``field.grad_max_pairs``: the (ray, sample) pairs one engine holds, ~16 GB of per-sample buffers
 PARAM_NAMES = ('plane_xy', 'plane_yz', 'plane_xz',
                'density_decoder.mlp.0.weight', 'density_decoder.mlp.0.bias', 'density_decoder.mlp.2.weight', 'density_decoder.mlp.2.bias',
                'density_decoder.mlp.4.weight', 'density_decoder.mlp.4.bias',
@@ -82,83 +84,50 @@ def _field_key(f, params):
             float(f.stepSize), float(f.distance_scale), float(f.rayMarch_weight_thres))
 
 
-class InfoInvGrad:
+class InfoInvGrad(GradEngine):
     """Device engine of one InfoInv field for batches of up to max_rays x max_samples (per-sample buffers ~4 KB per pair)."""
+    DESTROY, BYTES = "ngf_infoinv_trainer_destroy", "ngf_infoinv_trainer_bytes"
+    PARAMS_CHANGED, GET_GRADS = "ngf_infoinv_train_params_changed", "ngf_infoinv_train_get_grads"
+    STALE = slice(0, 3)             # the planes: the trainer keeps channel-last copies of them
 
     def __init__(self, field, max_rays, max_samples):
-        self.field = field
-        self.dev = torch.device(field.device)
-        if self.dev.type != "cuda":
+        dev = torch.device(field.device)
+        if dev.type != "cuda":
             raise RuntimeError("a differentiable InfoInv field(..., is_train=True) renders on the GPU only (device='cuda'); there is no CPU path")
-        self.L = _lib.lib()
+        params = train_params(field)
+        if params[0].is_cuda:
+            dev = params[0].device                    # 'cuda' -> 'cuda:k': where the parameters live
+        super().__init__(field, dev, params, max_rays, max_samples)
         _bind(self.L)
-        self.params = train_params(field)
-        if self.params[0].is_cuda:
-            self.dev = self.params[0].device          # 'cuda' -> 'cuda:k': where the parameters live
-        for name, p in zip(PARAM_NAMES, self.params):
-            if not (p.is_cuda and p.device == self.dev and p.dtype == torch.float32 and p.is_contiguous()):
-                raise RuntimeError(f"InfoInv training needs contiguous float32 parameters on {self.dev}: {name} is {p.dtype} on {p.device}")
-        self.max_rays, self.max_samples = int(max_rays), int(max_samples)
+        for name, p in zip(PARAM_NAMES, params):
+            if not (p.is_cuda and p.device == dev and p.dtype == torch.float32 and p.is_contiguous()):
+                raise RuntimeError(f"InfoInv training needs contiguous float32 parameters on {dev}: {name} is {p.dtype} on {p.device}")
         d = InfoInvTrainDesc()
-        ptr = [p.data_ptr() for p in self.params]
+        ptr = [p.data_ptr() for p in params]
         for k in range(3):
             d.plane[k] = ptr[k]
-            d.plane_h[k], d.plane_w[k] = int(self.params[k].shape[2]), int(self.params[k].shape[3])
+            d.plane_h[k], d.plane_w[k] = int(params[k].shape[2]), int(params[k].shape[3])
         (d.dens_w1, d.dens_b1, d.dens_w2, d.dens_b2, d.dens_w3, d.dens_b3) = ptr[3:9]
         (d.basis, d.w1, d.b1, d.w2, d.b2, d.w3, d.b3) = ptr[9:16]
-        d.aabb = (C.c_float * 6)(*field._aabb_host())
-        d.near_, d.far_ = float(field.near_far[0]), float(field.near_far[1])
-        d.step = float(field.stepSize)
-        d.distance_scale = float(field.distance_scale)
-        d.weight_thres = float(field.rayMarch_weight_thres)
-        self._keep = []
-        if field.alphaMask is not None:
-            bits = field.alphaMask.packed_bits_device().to(self.dev)
-            self._keep.append(bits)
-            d.mask_bits = bits.data_ptr()
-            shp = field.alphaMask.alpha_volume.shape
-            d.mask_d, d.mask_h, d.mask_w = int(shp[-3]), int(shp[-2]), int(shp[-1])
-            d.mask_aabb = (C.c_float * 6)(*field.alphaMask.aabb.reshape(-1).tolist())
+        self._keep = fill_geometry(d, field, dev, float(field.rayMarch_weight_thres))
         d.max_rays, d.max_samples = self.max_rays, self.max_samples
         out = C.c_void_p()
-        with torch.cuda.device(self.dev):
-            _lib.check(self.L.ngf_infoinv_trainer_create(C.byref(d), C.byref(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        with on_stream(dev) as st:
+            _lib.check(self.L.ngf_infoinv_trainer_create(C.byref(d), C.byref(out), st))
         self._h = out
-        self.key = _field_key(field, self.params)
-        self._versions = None                   # the first forward packs the planes
+        self.key = self._key(params)
         self.repacks = 0                        # how often the packed planes were marked stale (ngf_infoinv_train_params_changed)
         self._moments_owner = None              # the Trainer whose Adam moments the handle holds
         self.adam_ext = self.L.ngf_infoinv_train_adam_ext      # what ngf_amd.optim.Adam calls for this engine's parameters
         from . import optim
-        optim.register(field, self.params)      # ngf_amd.optim.Adam finds the engine behind a parameter (fused update, no re-pack)
+        optim.register(field, params)           # ngf_amd.optim.Adam finds the engine behind a parameter (fused update, no re-pack)
 
-    @property
-    def bytes(self) -> int:
-        return int(self.L.ngf_infoinv_trainer_bytes(self._h)) if self._h is not None else 0
-
-    def fits(self, n, S, params):
-        return n <= self.max_rays and S <= self.max_samples and self.key == _field_key(self.field, params)
-
-    def release(self):
-        if getattr(self, "_h", None) is not None:
-            self.L.ngf_infoinv_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
+    def _key(self, params):
+        return _field_key(self.field, params)
 
     def sync_planes(self):
-        """The packed planes follow torch's in-place version counters (optimizer.step(), load_state_dict); ``field.invalidate()`` marks them
-        stale for writes that bypass the counters.  The library's own Adam writes the packed copies itself and bumps nothing."""
-        v = tuple(int(p._version) for p in self.params[:3])
-        if v != self._versions or getattr(self.field, "_grad_stale", False):
-            _lib.check(self.L.ngf_infoinv_train_params_changed(self._h))
-            self.repacks += 1
-            self._versions = v
-            self.field._grad_stale = False
+        """``GradEngine.sync``, counted: the first forward packs the planes, later ones when a version counter moved or the field was invalidated."""
+        self.repacks += self.sync()
 
     def forward(self, rays, jitter, S, white_bg, infoinv):
         """-> (rgb_map [n,3], depth_map [n], ticket); see ``sync_planes`` for when the planes are packed again."""
@@ -167,24 +136,15 @@ class InfoInvGrad:
         rgb = torch.empty((n, 3), device=self.dev, dtype=torch.float32)
         depth = torch.empty((n,), device=self.dev, dtype=torch.float32)
         ticket = C.c_int64(0)
-        with torch.cuda.device(self.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        with on_stream(self.dev) as st:
             _lib.check(self.L.ngf_infoinv_train_forward(self._h, rays.data_ptr(), jitter.data_ptr(), n, int(S), int(bool(white_bg)),
                                                         int(bool(infoinv)), rgb.data_ptr(), depth.data_ptr(), C.byref(ticket), st))
         return rgb, depth, int(ticket.value)
 
     def backward(self, ticket, d_rgb, want):
         """``want[k]``: return parameter k's gradient (else None).  None = the ticket is stale (another forward used the buffers)."""
-        with torch.cuda.device(self.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            rc = self.L.ngf_infoinv_train_backward_grad(self._h, int(ticket), d_rgb.data_ptr(), st)
-            if rc == _lib.E_STALE:
-                return None
-            _lib.check(rc)
-            grads = [torch.empty_like(self.params[k]) if want[k] else None for k in range(NPARAMS)]
-            ptrs = (C.c_void_p * NPARAMS)(*[None if g is None else g.data_ptr() for g in grads])
-            _lib.check(self.L.ngf_infoinv_train_get_grads(self._h, ptrs, st))
-        return grads
+        with on_stream(self.dev) as st:
+            return self._grads(self.L.ngf_infoinv_train_backward_grad(self._h, int(ticket), d_rgb.data_ptr(), st), want, st)
 
 
 class _InfoInvRender(torch.autograd.Function):
@@ -205,28 +165,13 @@ class _InfoInvRender(torch.autograd.Function):
         saved = ctx.saved_tensors
         rays, jitter = saved[0], saved[1]
         S, white_bg, infoinv = ctx.cfg
-        eng = ctx.engine
-        if getattr(ctx.field, '_ii_engine', None) is not eng or eng._h is None:
-            eng = ctx.field._infoinv_grad_engine(rays.shape[0], S)
-        if any(a.data_ptr() != b.data_ptr() or a.shape != b.shape for a, b in zip(saved[2:], eng.params)):
-            raise RuntimeError("the field's parameter tensors were re-allocated between forward and backward")
-        d = d_rgb.to(dtype=torch.float32).contiguous()
-        want = [bool(w) for w in ctx.needs_input_grad[7:]]
-        grads = eng.backward(ctx.ticket, d, want) if eng is ctx.engine else None
-        if grads is None:           # another forward went through the engine since (or it is a new one): render this batch again, then its backward
-            _, _, ticket = eng.forward(rays, jitter, S, white_bg, infoinv)
-            grads = eng.backward(ticket, d, want)
-            if grads is None:
-                raise RuntimeError(_lib.lib().ngf_last_error().decode())
+        grads = replay(ctx.field, '_ii_engine', lambda: ctx.field._infoinv_grad_engine(rays.shape[0], S), ctx.engine, ctx.ticket, saved[2:],
+                       (rays, jitter, S, white_bg, infoinv), (d_rgb.to(dtype=torch.float32).contiguous(),),
+                       [bool(w) for w in ctx.needs_input_grad[7:]])
         return (None,) * 7 + tuple(grads)
 
 
-def _max_rays(field, S):
-    """The autograd path's rule (infoinv.TriPlane._render_train_infoinv): at most ``field.grad_max_pairs`` (ray, sample) pairs per ray chunk."""
-    return max(1, max(int(getattr(field, 'grad_max_pairs', 1 << 22)), int(S)) // int(S))
-
-
-class Trainer:
+class Trainer(TrainerBase):
     """Adam state + the fused training step of one InfoInv field (the body of InfoInv/main.py:262-330):
 
         output = field(rays_train, is_train=True, white_bg=white_bg, N_samples=nSamples, infoinv=infoinv)
@@ -237,33 +182,17 @@ class Trainer:
     ``step(rays_train, rgb_train)`` does that in two library calls on the field's differentiable engine (the autograd path keeps working on the
     same field); the nn.Parameters are updated in place.  Arguments as ``ngf_amd.train.Trainer``; learning rates per InfoInv/models/Field.py:27-37:
     the three planes at ``lr_init``, both decoders at ``lr_basis``.  There is no CPU path."""
+    NAMES = PARAM_NAMES
+    GET_GRAD = "ngf_infoinv_train_get_grad"
 
     def __init__(self, field, batch_size=4096, max_samples=None, lr_init=0.02, lr_basis=1e-3, lr_decay_iters=-1, lr_decay_target_ratio=0.1,
                  n_iters=30000, L1_reg_weight=L1_REG_WEIGHT, betas=(0.9, 0.99), eps=1e-8, frozen=(), state_from=None):
-        self.field = field
-        self.dev = torch.device(field.device)
-        if self.dev.type != "cuda":
+        if torch.device(field.device).type != "cuda":
             raise RuntimeError("ngf_amd.infoinv_train.Trainer runs on the GPU only (device='cuda'); there is no CPU path")
         self.L = _lib.lib()
         _bind(self.L)
-        self.params = train_params(field)
-        self.exp_avg = [torch.zeros_like(p) for p in self.params]
-        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
-        self.steps = [0] * NPARAMS                  # torch.optim.Adam keeps one step counter per parameter
-        self.frozen = set(PARAM_NAMES.index(k) if isinstance(k, str) else int(k) for k in frozen)
-        self.lr = [lr_init] * 3 + [lr_basis] * (NPARAMS - 3)
-        self.lr_factor = lr_decay_target_ratio ** (1 / (lr_decay_iters if lr_decay_iters > 0 else n_iters))
-        self.betas, self.eps, self.l1 = betas, eps, L1_reg_weight
-        self.batch_size = int(batch_size)
-        self.max_samples = int(max_samples if max_samples is not None else field.nSamples)
-        if state_from is not None:                  # carry the optimiser state of parameters that kept their shape
-            for k in range(NPARAMS):
-                if state_from.exp_avg[k].shape == self.exp_avg[k].shape:
-                    self.exp_avg[k].copy_(state_from.exp_avg[k])
-                    self.exp_avg_sq[k].copy_(state_from.exp_avg_sq[k])
-                    self.steps[k] = state_from.steps[k]
-            self.lr = list(state_from.lr)
-        self._loss = torch.zeros((2,), dtype=torch.float64, device=self.dev)      # [sum of squared residuals, their mean]
+        super().__init__(field, train_params(field), [lr_init] * 3 + [lr_basis] * (NPARAMS - 3), batch_size, max_samples, lr_decay_iters,
+                         lr_decay_target_ratio, n_iters, L1_reg_weight, betas, eps, frozen, state_from)
         self._eng = None
         self._have_grads = False
         self._shape_key = _field_key(field, self.params)
@@ -272,7 +201,7 @@ class Trainer:
     def _engine(self, n, S):
         """The field's engine, sized for one ray chunk of the batch; this trainer's moments are the ones its handle updates."""
         f = self.field
-        per = _max_rays(f, S)
+        per = rays_per_chunk(f, S, MAX_PAIRS)      # the autograd path's rule (infoinv.TriPlane._render_train_infoinv)
         eng = getattr(f, '_ii_engine', None)
         if eng is not None and eng._h is not None and n > per and eng.max_rays > per:
             f.release_grad_engine()                 # built for more pairs than grad_max_pairs allows now: the library chunks by the engine's size
@@ -308,36 +237,20 @@ class Trainer:
         place.  Read it (``.item()``) before the next step, or pass ``keep_loss=True`` for a fresh tensor per step."""
         if _field_key(self.field, train_params(self.field)) != self._shape_key:
             raise RuntimeError("the field's parameters, alpha mask or geometry were re-allocated (load / a new mask): build a new Trainer")
-        rays = rays_train.to(device=self.dev, dtype=torch.float32).contiguous()
-        tgt = rgb_train.to(device=self.dev, dtype=torch.float32).contiguous()
-        n = rays.shape[0]
-        if rays.dim() != 2 or rays.shape[1] != 6 or tuple(tgt.shape) != (n, 3) or n == 0:
-            raise ValueError(f"rays_train must be [n,6] and rgb_train [n,3] with n > 0, got {tuple(rays.shape)} / {tuple(tgt.shape)}")
-        S = int(N_samples) if N_samples > 0 else int(self.field.nSamples)
-        if jitter is None:
-            jitter = torch.rand((n,), device=self.dev)                 # FieldBase.py:128-130
-        jitter = jitter.to(device=self.dev, dtype=torch.float32).reshape(n).contiguous()
-        white = bool(white_bg or ((float(torch.rand((1,))) if coin is None else float(coin)) < 0.5))      # FieldBase.py:270
+        rays, tgt, n, S, jitter, white = self._batch(rays_train, rgb_train, N_samples, white_bg, jitter, coin)
+        jitter = jitter.reshape(n)
         eng = self._engine(n, S)
         eng.sync_planes()
-        with torch.cuda.device(eng.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        with on_stream(eng.dev) as st:
             _lib.check(self.L.ngf_infoinv_train_step_backward(eng._h, rays.data_ptr(), tgt.data_ptr(), jitter.data_ptr(), n, S, int(white),
                                                               int(bool(infoinv)), self._loss.data_ptr(), st))
         self._have_grads = True
-        return self._loss[1].clone() if keep_loss else self._loss[1]
+        return self._loss_out(keep_loss)
 
-    @torch.no_grad()
-    def gradient(self, which) -> torch.Tensor:
-        """The gradient of one parameter (index or state_dict name) in its reference layout, after ``backward``.  Planes exclude the L1 term
-        (it is added inside the Adam kernel)."""
-        k = PARAM_NAMES.index(which) if isinstance(which, str) else int(which)
+    def _grad_handle(self):
         if self._eng is None or self._eng._h is None or not self._have_grads:
             raise RuntimeError("gradient() needs a backward() first")
-        out = torch.empty_like(self.params[k])
-        with torch.cuda.device(self._eng.dev):
-            _lib.check(self.L.ngf_infoinv_train_get_grad(self._eng._h, k, out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return out
+        return self._eng._h, self._eng.dev
 
     @torch.no_grad()
     def optimizer_step(self):
@@ -349,28 +262,14 @@ class Trainer:
             raise RuntimeError("optimizer_step() needs a backward() first")
         if eng._moments_owner is not self:
             raise RuntimeError("another Trainer used this field's engine since the backward: run backward() again")
-        counts = (C.c_int32 * NPARAMS)()
-        for k in range(NPARAMS):
-            if k in self.frozen:
-                continue                              # count 0 = skipped
-            self.steps[k] += 1
-            counts[k] = self.steps[k]
-        lrs = (C.c_float * NPARAMS)(*[float(x) for x in self.lr])
-        with torch.cuda.device(eng.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        counts, lrs, _ = self._advance()
+        with on_stream(eng.dev) as st:
             _lib.check(self.L.ngf_infoinv_train_adam_all(eng._h, counts, lrs, float(self.betas[0]), float(self.betas[1]), float(self.eps),
                                                          float(self.l1), st))
         self._have_grads = False         # one update per backward: a second optimizer_step() raises instead of applying the gradients again
         self.field.invalidate()          # parameters changed behind torch's back: the eval image is re-packed on the next render ...
         self.field._grad_stale = False   # ... but the engine's packed planes were written by the Adam pass itself
-        self.lr = [x * self.lr_factor for x in self.lr]
-
-    def step(self, rays_train, rgb_train, N_samples=-1, white_bg=True, infoinv=True, jitter=None, coin=None, keep_loss=False):
-        """One iteration of main.py:262-330.  Returns the rgb loss (0-dim float64 device tensor; ``.item()`` for PSNR) -- a view of the trainer's
-        loss buffer that the next step overwrites unless ``keep_loss=True`` (see ``backward``)."""
-        loss = self.backward(rays_train, rgb_train, N_samples, white_bg, infoinv, jitter, coin, keep_loss=keep_loss)
-        self.optimizer_step()
-        return loss
+        self._decay()
 
 
 def fit(field, allrays, allrgbs, args, white_bg=True, infoinv=True, on_iteration=None):

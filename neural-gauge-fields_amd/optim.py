@@ -15,6 +15,7 @@ copies stale).  Parameters that do not belong to a field with a live differentia
 maximize, capturable or differentiable -- take torch's own path (``super().step()``), so the class is a superset, not a special case.
 An InfoInv field (``ngf_amd.infoinv.TriPlane`` with ``differentiable = True``) is taken the same way: its sixteen parameters go through
 ``ngf_infoinv_train_adam_ext`` once its differentiable engine is live, and the next differentiable forward packs nothing.
+Both engines are ``_engine.GradEngine`` subclasses (``_h``, ``dev``, ``params``); this class asks nothing else of them but ``adam_ext``.
 There is no CPU path for the fused part; on CPU tensors everything is torch's."""
 from __future__ import annotations
 
@@ -25,8 +26,9 @@ import torch
 
 from . import _lib
 
-# id(parameter) -> (weak parameter, weak field, index in train.PARAM_NAMES); filled by train.RenderGrad when a field's differentiable engine is
-# built (and by infoinv_train.InfoInvGrad, with the index in infoinv_train.PARAM_NAMES).  (Keyed by id: a tensor cannot key a WeakKeyDictionary -- its == is elementwise.)
+# id(parameter) -> (weak parameter, weak field, index in the engine's ``params``); filled when a field's differentiable engine is built, by the two
+# _engine.GradEngine subclasses that have an ``adam_ext``: train.RenderGrad (index in train.PARAM_NAMES) and infoinv_train.InfoInvGrad (index in
+# infoinv_train.PARAM_NAMES).  (Keyed by id: a tensor cannot key a WeakKeyDictionary -- its == is elementwise.)
 _OWNERS = {}
 
 

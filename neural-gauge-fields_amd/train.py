@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine import GradEngine, Handle, TrainerBase, fill_geometry, on_stream, replay
 
 PARAM_NAMES = ("plane_xy", "plane_yz", "plane_xz", "gauge_xy", "gauge_yz", "gauge_xz", "density_decoder.weight",
                "density_decoder.bias", "rgb_decoder.basis.weight", "rgb_decoder.mlp.0.weight", "rgb_decoder.mlp.0.bias",
@@ -92,12 +93,6 @@ def _train_params(field):
 def _train_desc(f, params, exp_avg, exp_avg_sq, max_rays, max_samples, chunk_samples):
     """ngf_train_desc of field ``f``; ``exp_avg`` / ``exp_avg_sq`` None = a trainer without optimiser (ngf_train_forward / _backward_grad only)."""
     d = TrainDesc()
-    dev = torch.device(f.device)
-    d.aabb = (C.c_float * 6)(*f._aabb_host())
-    d.near_, d.far_ = float(f.near_far[0]), float(f.near_far[1])
-    d.step = float(f.stepSize)
-    d.distance_scale = float(f.distance_scale)
-    d.weight_thres = float(np.float32(f.rayMarch_weight_thres))
     for k in range(3):
         d.plane[k] = params[k].data_ptr()
         d.plane_h[k], d.plane_w[k] = params[k].shape[2], params[k].shape[3]
@@ -108,14 +103,7 @@ def _train_desc(f, params, exp_avg, exp_avg_sq, max_rays, max_samples, chunk_sam
         for k in range(15):
             d.exp_avg[k] = exp_avg[k].data_ptr()
             d.exp_avg_sq[k] = exp_avg_sq[k].data_ptr()
-    keep = []
-    if f.alphaMask is not None:
-        bits = f.alphaMask.packed_bits_device().to(dev)
-        keep.append(bits)
-        d.mask_bits = bits.data_ptr()
-        shp = f.alphaMask.alpha_volume.shape
-        d.mask_d, d.mask_h, d.mask_w = int(shp[-3]), int(shp[-2]), int(shp[-1])
-        d.mask_aabb = (C.c_float * 6)(*f.alphaMask.aabb.reshape(-1).tolist())
+    keep = fill_geometry(d, f, torch.device(f.device), float(np.float32(f.rayMarch_weight_thres)))
     d.max_rays, d.max_samples, d.chunk_samples = int(max_rays), int(max_samples), int(chunk_samples)
     return d, keep
 
@@ -126,11 +114,14 @@ def _field_key(f, params):
             tuple(f.near_far), float(f.distance_scale), float(f.rayMarch_weight_thres))
 
 
-class Trainer:
+class Trainer(TrainerBase, Handle):
     """Adam state + the device trainer of one TriPlane field.
 
     ``lr_init`` / ``lr_basis`` / ``lr_decay_*`` / ``n_iters`` are the flags of TriPlane/opt.py; ``batch_size`` and
     ``max_samples`` size the scratch buffers (args.batch_size and the largest N_samples that will be passed)."""
+    NAMES = PARAM_NAMES
+    DESTROY, GET_GRAD = "ngf_trainer_destroy", "ngf_train_get_grad"
+    EMPTY_OK = True
 
     def __init__(self, field, batch_size=4096, max_samples=None, lr_init=0.02, lr_basis=1e-3, lr_decay_iters=-1,
                  lr_decay_target_ratio=0.1, n_iters=30000, L1_reg_weight=L1_REG_WEIGHT, betas=(0.9, 0.99), eps=1e-8, chunk_samples=None,
@@ -150,27 +141,13 @@ class Trainer:
 
         An explicit ``chunk_samples``: ``0`` = rows for every pair (never overflows, no synchronisation); ``> 0`` = that many rows, host count
         (the default's path); ``< 0`` = speculative with that many rows."""
-        self.field = field
-        self.dev = torch.device(field.device)
-        if self.dev.type != "cuda":
+        if torch.device(field.device).type != "cuda":
             raise RuntimeError("ngf_amd.train.Trainer runs on the GPU only (device='cuda'); there is no CPU path")
         self.L = _lib.lib()
         _bind(self.L)
-        self.params = _train_params(field)
-        self.exp_avg = [torch.zeros_like(p) for p in self.params]
-        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
-        self.steps = [0] * 15                       # torch.optim.Adam keeps one step counter per parameter
-        self.frozen = set(int(k) for k in frozen)   # parameter indices optimizer_step leaves alone
-        # get_optparam_groups (Field.py:34-46)
-        net = lr_basis
-        self.lr = [lr_init] * 3 + [net * 0.1] * 3 + [net] * 9
-        if lr_decay_iters > 0:
-            self.lr_factor = lr_decay_target_ratio ** (1 / lr_decay_iters)
-        else:
-            self.lr_factor = lr_decay_target_ratio ** (1 / n_iters)
-        self.betas, self.eps, self.l1 = betas, eps, L1_reg_weight
-        self.batch_size = int(batch_size)
-        self.max_samples = int(max_samples if max_samples is not None else field.nSamples)
+        # learning rates: get_optparam_groups (Field.py:34-46)
+        super().__init__(field, _train_params(field), [lr_init] * 3 + [lr_basis * 0.1] * 3 + [lr_basis] * 9, batch_size, max_samples,
+                         lr_decay_iters, lr_decay_target_ratio, n_iters, L1_reg_weight, betas, eps, frozen, state_from)
         pairs = self.batch_size * self.max_samples
         if chunk_samples is None:
             rows = (max(1 << 18, -(-pairs // 3)) + 15) // 16 * 16
@@ -180,15 +157,6 @@ class Trainer:
         self._since_check = 0
         self._applied = []                          # speculative rows: (parameter indices, lr factor) of the optimizer steps since the last check
         self._overflows_seen = 0
-        self._h = None
-        if state_from is not None:                  # carry the optimiser state of parameters that kept their shape
-            for k in range(15):
-                if state_from.exp_avg[k].shape == self.exp_avg[k].shape:
-                    self.exp_avg[k].copy_(state_from.exp_avg[k])
-                    self.exp_avg_sq[k].copy_(state_from.exp_avg_sq[k])
-                    self.steps[k] = state_from.steps[k]
-            self.lr = list(state_from.lr)
-        self._loss = torch.zeros((2,), dtype=torch.float64, device=self.dev)      # [sum of squared residuals, their mean]
         self._active = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self._gauge_on = True          # set by backward(); optimizer_step() before any backward() updates nothing but must not raise
         self._build()
@@ -196,8 +164,8 @@ class Trainer:
     def _build(self):
         d, self._keep = _train_desc(self.field, self.params, self.exp_avg, self.exp_avg_sq, self.batch_size, self.max_samples, self.chunk_samples)
         out = C.c_void_p()
-        with torch.cuda.device(self.dev):
-            _lib.check(self.L.ngf_trainer_create(C.byref(d), C.byref(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        with on_stream(self.dev) as st:
+            _lib.check(self.L.ngf_trainer_create(C.byref(d), C.byref(out), st))
         self.release()
         self._h = out
         self._shape_key = self._key()
@@ -213,17 +181,6 @@ class Trainer:
         ``frozen=`` parameter, ``.mul_()``.  (``.data`` writes and raw-pointer writes bump nothing: ``params_changed()`` is for them.)"""
         return tuple(int(p._version) for p in self.params[:6])
 
-    def release(self):
-        if getattr(self, "_h", None) is not None:
-            self.L.ngf_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
     def params_changed(self):
         """Tell the trainer that plane / gauge-plane values were written by something other than ``optimizer_step`` (an in-place
         edit, ``load_state_dict``): its channel-last copies are rebuilt on the next ``backward``."""
@@ -236,8 +193,8 @@ class Trainer:
         """(steps whose batch had more active samples than the trainer keeps activation rows for -- their updates were skipped on the
         device --, the row count).  Synchronises with the device."""
         cnt, rows = C.c_int64(0), C.c_int64(0)
-        with torch.cuda.device(self.dev):
-            _lib.check(self.L.ngf_train_overflow_count(self._h, C.byref(cnt), C.byref(rows), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        with on_stream(self.dev) as st:
+            _lib.check(self.L.ngf_train_overflow_count(self._h, C.byref(cnt), C.byref(rows), st))
         return int(cnt.value), int(rows.value)
 
     def check_rows(self, grow=True) -> int:
@@ -275,8 +232,7 @@ class Trainer:
         n = getattr(self, "_last_n", 0)
         if n <= 0:
             return 0
-        with torch.cuda.device(self.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        with on_stream(self.dev) as st:
             _lib.check(self.L.ngf_train_get_active(self._h, n, self._active.data_ptr(), st))
         return int(self._active.item())
 
@@ -295,58 +251,29 @@ class Trainer:
         if self._param_versions() != self._versions:      # an in-place write from outside: the packed copies are stale
             self.params_changed()
             self._versions = self._param_versions()
-        rays = rays_train.to(device=self.dev, dtype=torch.float32).contiguous()
-        tgt = rgb_train.to(device=self.dev, dtype=torch.float32).contiguous()
-        n = rays.shape[0]
-        if rays.dim() != 2 or rays.shape[1] != 6 or tuple(tgt.shape) != (n, 3):
-            raise ValueError(f"rays_train must be [n,6] and rgb_train [n,3], got {tuple(rays.shape)} / {tuple(tgt.shape)}")
-        S = int(N_samples) if N_samples > 0 else int(self.field.nSamples)
-        if jitter is None:
-            jitter = torch.rand((n,), device=self.dev)                 # FieldBase.py:129-130
-        jitter = jitter.to(device=self.dev, dtype=torch.float32).contiguous()
-        if not white_bg:
-            c = float(torch.rand((1,))) if coin is None else float(coin)   # FieldBase.py:299
-            white_bg = c < 0.5
+        rays, tgt, n, S, jitter, white = self._batch(rays_train, rgb_train, N_samples, white_bg, jitter, coin)
         gauge_on = int(iteration >= self.field.gauge_start)
         # no host pointer for the active count: the call stays asynchronous (the colour kernels read the count on the device);
         # ``last_active`` fetches it lazily
-        with torch.cuda.device(self.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(self.L.ngf_train_backward2(self._h, rays.data_ptr(), tgt.data_ptr(), jitter.data_ptr(), n, S, int(bool(white_bg)), gauge_on,
+        with on_stream(self.dev) as st:
+            _lib.check(self.L.ngf_train_backward2(self._h, rays.data_ptr(), tgt.data_ptr(), jitter.data_ptr(), n, S, int(white), gauge_on,
                                                   self._loss.data_ptr(), int(self._loss.numel()), None, st))
         self._last_n = n
         self._gauge_on = gauge_on
-        # a view: the division is done by the step's last kernel (a torch op here is one more launch per step)
-        return self._loss[1].clone() if keep_loss else self._loss[1]
+        return self._loss_out(keep_loss)
 
-    @torch.no_grad()
-    def gradient(self, which) -> torch.Tensor:
-        """The gradient of one parameter (index or state_dict name) in its reference layout, after ``backward``.
-        Planes exclude the L1 term (it is added inside the Adam kernel)."""
-        k = PARAM_NAMES.index(which) if isinstance(which, str) else int(which)
-        out = torch.empty_like(self.params[k])
-        with torch.cuda.device(self.dev):
-            _lib.check(self.L.ngf_train_get_grad(self._h, k, out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return out
+    def _skipped(self, k):
+        return 3 <= k < 6 and not self._gauge_on
 
     @torch.no_grad()
     def optimizer_step(self):
         """optimizer.step() + the lr decay of main.py:298-299.  Gauge planes without a gradient (iteration <
         gauge_start) are skipped like torch.optim skips parameters whose .grad is None."""
-        counts = (C.c_int32 * 15)()
-        idx = []
-        for k in range(15):
-            if (3 <= k < 6 and not self._gauge_on) or k in self.frozen:
-                continue                              # count 0 = skipped
-            self.steps[k] += 1
-            counts[k] = self.steps[k]
-            idx.append(k)
-        lrs = (C.c_float * 15)(*[float(x) for x in self.lr])
-        with torch.cuda.device(self.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        counts, lrs, idx = self._advance()
+        with on_stream(self.dev) as st:
             _lib.check(self.L.ngf_train_adam_all(self._h, counts, lrs, float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.l1), st))
         self.field.invalidate()      # parameters changed behind torch's back: the eval image is re-packed on the next render
-        self.lr = [x * self.lr_factor for x in self.lr]
+        self._decay()
         if self.chunk_samples < 0:   # speculative rows: the device may have refused this update -- look every check_every steps
             self._applied.append((idx, self.lr_factor))
             self._since_check += 1
@@ -354,14 +281,11 @@ class Trainer:
                 self.check_rows()
 
     def step(self, rays_train, rgb_train, iteration, N_samples=-1, white_bg=True, jitter=None, coin=None, keep_loss=False):
-        """One iteration of main.py:264-299.  Returns the rgb loss (0-dim float64 device tensor; ``.item()`` for PSNR) -- a view of the
-        trainer's loss buffer that the next step overwrites unless ``keep_loss=True`` (see ``backward``)."""
-        loss = self.backward(rays_train, rgb_train, N_samples, white_bg, iteration, jitter, coin, keep_loss=keep_loss)
-        self.optimizer_step()
-        return loss
+        """One iteration of main.py:264-299 (``TrainerBase.step`` with the loop's argument order)."""
+        return super().step(rays_train, rgb_train, N_samples, white_bg, iteration, jitter, coin, keep_loss=keep_loss)
 
 
-class RenderGrad:
+class RenderGrad(GradEngine):
     """The device side of a DIFFERENTIABLE ``field(rays, is_train=True)`` (TriPlane/models/FieldBase.py:251-312 under autograd, as the reference's
     training loop uses it, TriPlane/main.py:272-296): a device trainer without optimiser state, driven in two calls -- ``forward`` renders the
     batch in training mode with the trainer's kernels and keeps its per-sample buffers, ``backward`` takes d loss / d rgb_map and returns the
@@ -377,15 +301,15 @@ class RenderGrad:
       the reference's own ``rgb_mask.any()`` (FieldBase.py:291): a batch with more active samples than rows is worked through chunk by chunk.
     ``field.grad_rows = "all" | "third"`` forces one or the other."""
 
+    DESTROY, BYTES, PARAMS_CHANGED, GET_GRADS = "ngf_trainer_destroy", "ngf_trainer_bytes", "ngf_train_params_changed", "ngf_train_get_grads"
+    STALE = slice(0, 6)             # the plane and gauge-plane tensors: the trainer keeps channel-last copies of them
+
     def __init__(self, field, max_rays, max_samples):
-        self.field = field
-        self.dev = torch.device(field.device)
-        if self.dev.type != "cuda":
+        dev = torch.device(field.device)
+        if dev.type != "cuda":
             raise RuntimeError("a differentiable field(..., is_train=True) renders on the GPU only (device='cuda'); there is no CPU path")
-        self.L = _lib.lib()
+        super().__init__(field, dev, _train_params(field), max_rays, max_samples)
         _bind(self.L)
-        self.params = _train_params(field)
-        self.max_rays, self.max_samples = int(max_rays), int(max_samples)
         pairs = self.max_rays * self.max_samples
         rows = min(pairs, max(1 << 18, -(-pairs // 3)))
         self.chunk_samples = (rows + 15) // 16 * 16
@@ -397,11 +321,11 @@ class RenderGrad:
             self.chunk_samples = 0                  # ngf_train_desc: rows for every pair -- no host count, no chunks
         d, self._keep = _train_desc(field, self.params, None, None, self.max_rays, self.max_samples, self.chunk_samples)
         out = C.c_void_p()
-        with torch.cuda.device(self.dev):
-            _lib.check(self.L.ngf_trainer_create(C.byref(d), C.byref(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        with on_stream(self.dev) as st:
+            _lib.check(self.L.ngf_trainer_create(C.byref(d), C.byref(out), st))
         self._h = out
-        self.key = _field_key(field, self.params)
-        self._versions = tuple(int(p._version) for p in self.params[:6])
+        self.key = self._key(self.params)
+        self._versions = tuple(int(p._version) for p in self.params[self.STALE])      # create packed the planes as they are now
         self._last_active, self._last_n = 0, 0
         self._active_dev = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self.adam_ext = self.L.ngf_train_adam_ext       # what ngf_amd.optim.Adam calls for this engine's parameters
@@ -412,56 +336,33 @@ class RenderGrad:
     def last_active(self) -> int:
         """Active samples of the last forward (read from the device on demand when the forward did not bring it to the host)."""
         if not self.host_count and self._last_n > 0 and self._h is not None:
-            with torch.cuda.device(self.dev):
-                _lib.check(self.L.ngf_train_get_active(self._h, self._last_n, self._active_dev.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            with on_stream(self.dev) as st:
+                _lib.check(self.L.ngf_train_get_active(self._h, self._last_n, self._active_dev.data_ptr(), st))
             return int(self._active_dev.item())
         return self._last_active
 
-    def fits(self, n, S, params=None):
-        return n <= self.max_rays and S <= self.max_samples and self.key == _field_key(self.field, _train_params(self.field) if params is None else params)
-
-    def release(self):
-        if getattr(self, "_h", None) is not None:
-            self.L.ngf_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
+    def _key(self, params):
+        return _field_key(self.field, params)
 
     def forward(self, rays, jitter, S, white_bg, gauge_on):
         """-> (rgb_map [n,3], depth_map [n], ticket).  The planes' packed copies follow torch's in-place version counters (optimizer.step(),
-        load_state_dict); ``field.invalidate()`` marks them stale for writes that bypass the counters."""
-        v = tuple(int(p._version) for p in self.params[:6])
-        if v != self._versions or getattr(self.field, "_grad_stale", False):
-            _lib.check(self.L.ngf_train_params_changed(self._h))
-            self._versions = v
-            self.field._grad_stale = False
+        load_state_dict); ``field.invalidate()`` marks them stale for writes that bypass the counters (``GradEngine.sync``)."""
+        self.sync()
         n = rays.shape[0]
         rgb = torch.empty((n, 3), device=self.dev, dtype=torch.float32)
         depth = torch.empty((n,), device=self.dev, dtype=torch.float32)
         n_active, ticket = C.c_int64(0), C.c_int64(0)
-        with torch.cuda.device(self.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        with on_stream(self.dev) as st:
             _lib.check(self.L.ngf_train_forward(self._h, rays.data_ptr(), jitter.data_ptr(), n, int(S), int(bool(white_bg)), int(bool(gauge_on)),
                                                 rgb.data_ptr(), depth.data_ptr(), C.byref(n_active) if self.host_count else None, C.byref(ticket), st))
         self._last_active, self._last_n = int(n_active.value), n
         return rgb, depth, int(ticket.value)
 
     def backward(self, ticket, d_rgb, want):
-        """``want[k]``: return parameter k's gradient (else None).  None = the ticket is stale (NGF_E_STALE: another forward used the buffers) -- re-run forward; every other failure raises."""
-        with torch.cuda.device(self.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            rc = self.L.ngf_train_backward_grad(self._h, int(ticket), d_rgb.data_ptr(), st)
-            if rc == _lib.E_STALE:
-                return None
-            _lib.check(rc)              # anything else is an error of this call (a HIP / launch failure must not be retried away)
-            grads = [torch.empty_like(self.params[k]) if want[k] else None for k in range(15)]
-            ptrs = (C.c_void_p * 15)(*[None if g is None else g.data_ptr() for g in grads])
-            _lib.check(self.L.ngf_train_get_grads(self._h, ptrs, st))          # one call: three tiled transposes, the gauge planes, one launch for the nine MLP tensors
-        return grads
+        """``want[k]``: return parameter k's gradient (else None); None = the ticket is stale, re-run forward (``GradEngine._grads``: one get_grads
+        call -- three tiled transposes, the gauge planes, one launch for the nine MLP tensors)."""
+        with on_stream(self.dev) as st:
+            return self._grads(self.L.ngf_train_backward_grad(self._h, int(ticket), d_rgb.data_ptr(), st), want, st)
 
 
 class _TrainRender(torch.autograd.Function):
@@ -482,23 +383,11 @@ class _TrainRender(torch.autograd.Function):
         saved = ctx.saved_tensors
         rays, jitter = saved[0], saved[1]
         S, white_bg, gauge_on = ctx.cfg
-        # the field's CURRENT engine: the one of the forward (the common case: its identity is the whole check), unless a larger batch or a
-        # re-allocation had it rebuilt in between (then this batch is rendered again below)
-        eng = ctx.engine
-        if getattr(ctx.field, '_grad_engine', None) is not eng or eng._h is None:
-            eng = ctx.field._render_grad_engine(rays.shape[0], S)
-        if any(a.data_ptr() != b.data_ptr() or a.shape != b.shape for a, b in zip(saved[2:], eng.params)):
-            raise RuntimeError("the field's parameter tensors were re-allocated (up_sampling / shrink / load) between forward and backward")
-        d = d_rgb.to(dtype=torch.float32).contiguous()
         want = [bool(w) for w in ctx.needs_input_grad[7:]]
         if not gauge_on:                                   # compute_gauge was not evaluated (Field.py:58,73): the gauge planes are not in the graph
             want[3:6] = [False, False, False]
-        grads = eng.backward(ctx.ticket, d, want) if eng is ctx.engine else None
-        if grads is None:                                  # another forward went through the engine since (or the engine is a new one): render this batch again, then its backward
-            _, _, ticket = eng.forward(rays, jitter, S, white_bg, gauge_on)
-            grads = eng.backward(ticket, d, want)
-            if grads is None:
-                raise RuntimeError(_lib.lib().ngf_last_error().decode())
+        grads = replay(ctx.field, '_grad_engine', lambda: ctx.field._render_grad_engine(rays.shape[0], S), ctx.engine, ctx.ticket, saved[2:],
+                       (rays, jitter, S, white_bg, gauge_on), (d_rgb.to(dtype=torch.float32).contiguous(),), want)
         return (None,) * 7 + tuple(grads)
 
 

@@ -12,6 +12,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._engine import GradEngine, on_stream, replay
 
 NPARAMS = 2 * _lib.UV_LAYERS
 
@@ -77,71 +78,51 @@ def train_params(net):
     return out
 
 
-class UvGrad:
+class UvGrad(GradEngine):
     """Device engine of one NeuTex for batches of up to max_rays x max_samples (about 27 KB of per-sample buffers per (ray, sample) pair)."""
+    DESTROY, BYTES, PARAMS_CHANGED, GET_GRADS = "ngf_uv_trainer_destroy", "ngf_uv_trainer_bytes", "ngf_uv_train_params_changed", "ngf_uv_train_get_grads"
+    # STALE: every tensor.  The weights are read in place; a change of any tensor's version (optimizer.step(), load_state_dict) is reported to
+    # the trainer (it packs nothing today, the call is its contract).  A NeuTex has no ``_grad_stale``.
+    FIELD_STALE = False
+    GROWS_FROM_RELEASED = False
 
     def __init__(self, net, max_rays, max_samples):
-        self.net = net
-        self.L = _lib.lib()
-        _bind(self.L)
-        self.params = train_params(net)
-        self.dev = self.params[0].device
-        if self.dev.type != "cuda":
+        params = train_params(net)
+        dev = params[0].device
+        if dev.type != "cuda":
             raise RuntimeError("a differentiable NeuTex renders on the GPU only (device='cuda'); there is no CPU path")
-        for p in self.params:
-            if not (p.is_cuda and p.device == self.dev and p.dtype == torch.float32 and p.is_contiguous()):
-                raise RuntimeError(f"UV-Mapping training needs contiguous float32 parameters on {self.dev}: one is {p.dtype} on {p.device}")
-        self.max_rays, self.max_samples = int(max_rays), int(max_samples)
+        super().__init__(net, dev, params, max_rays, max_samples)
+        _bind(self.L)
+        self.net = net
+        for p in params:
+            if not (p.is_cuda and p.device == dev and p.dtype == torch.float32 and p.is_contiguous()):
+                raise RuntimeError(f"UV-Mapping training needs contiguous float32 parameters on {dev}: one is {p.dtype} on {p.device}")
         d = UvTrainDesc()
         d.sphere = int(net.primitive_type != 'square')
         d.flags = 0
         for i in range(_lib.UV_LAYERS):
-            d.w[i], d.b[i] = self.params[2 * i].data_ptr(), self.params[2 * i + 1].data_ptr()
+            d.w[i], d.b[i] = params[2 * i].data_ptr(), params[2 * i + 1].data_ptr()
         d.max_rays, d.max_samples = self.max_rays, self.max_samples
         out = C.c_void_p()
-        with torch.cuda.device(self.dev):
-            _lib.check(self.L.ngf_uv_trainer_create(C.byref(d), C.byref(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        with on_stream(dev) as st:
+            _lib.check(self.L.ngf_uv_trainer_create(C.byref(d), C.byref(out), st))
         self._h = out
-        self.key = self._key(self.params)
-        self._versions = None
+        self.key = self._key(params)
 
     @staticmethod
     def _key(params):
         return tuple((p.data_ptr(), tuple(p.shape)) for p in params)
 
-    @property
-    def bytes(self) -> int:
-        return int(self.L.ngf_uv_trainer_bytes(self._h)) if self._h is not None else 0
-
-    def fits(self, nrays, S, params):
-        return nrays <= self.max_rays and S <= self.max_samples and self.key == self._key(params)
-
-    def release(self):
-        if getattr(self, "_h", None) is not None:
-            self.L.ngf_uv_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
     def forward(self, cam, rd, bg, U):
-        """-> (color [N,R,3], trans [N,R], uv [N,R,S,D], weight [N,R,S], ray_pos [N,R,S,3], ticket).  The weights are read in place; a change of
-        any tensor's version (optimizer.step(), load_state_dict) is reported to the trainer (it packs nothing today, the call is its contract)."""
-        v = tuple(int(p._version) for p in self.params)
-        if v != self._versions:
-            _lib.check(self.L.ngf_uv_train_params_changed(self._h))
-            self._versions = v
+        """-> (color [N,R,3], trans [N,R], uv [N,R,S,D], weight [N,R,S], ray_pos [N,R,S,3], ticket)."""
+        self.sync()
         N, R, S = U.shape
         D = 2 if self.net.primitive_type == 'square' else 3
         f = dict(device=self.dev, dtype=torch.float32)
         color, trans = torch.empty((N, R, 3), **f), torch.empty((N, R), **f)
         uv, weight, pos = torch.empty((N, R, S, D), **f), torch.empty((N, R, S), **f), torch.empty((N, R, S, 3), **f)
         ticket = C.c_int64(0)
-        with torch.cuda.device(self.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        with on_stream(self.dev) as st:
             _lib.check(self.L.ngf_uv_train_forward(self._h, cam.data_ptr(), rd.data_ptr(), None if bg is None else bg.data_ptr(), U.data_ptr(), N, R, S,
                                                    color.data_ptr(), trans.data_ptr(), uv.data_ptr(), weight.data_ptr(), pos.data_ptr(),
                                                    C.byref(ticket), st))
@@ -149,21 +130,14 @@ class UvGrad:
 
     def backward(self, ticket, d_color, d_trans, d_uv, d_weight, want):
         """``want[k]``: return tensor k's gradient (else None).  None = the ticket is stale (another forward used the buffers)."""
-        with torch.cuda.device(self.dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        with on_stream(self.dev) as st:
             rc = self.L.ngf_uv_train_backward(self._h, int(ticket), d_color.data_ptr(), d_trans.data_ptr(),
                                               None if d_uv is None else d_uv.data_ptr(), None if d_weight is None else d_weight.data_ptr(), st)
-            if rc == _lib.E_STALE:
-                return None
-            _lib.check(rc)
-            grads = [torch.empty_like(self.params[k]) if want[k] else None for k in range(NPARAMS)]
-            ptrs = (C.c_void_p * NPARAMS)(*[None if g is None else g.data_ptr() for g in grads])
-            _lib.check(self.L.ngf_uv_train_get_grads(self._h, ptrs, st))
-        return grads
+            return self._grads(rc, want, st)
 
 
-def _grad_or_zeros(g, like):
-    return torch.zeros_like(like) if g is None else g.to(dtype=torch.float32).contiguous()
+def _f32(g):
+    return None if g is None else g.to(dtype=torch.float32).contiguous()
 
 
 class _UvRender(torch.autograd.Function):
@@ -186,24 +160,11 @@ class _UvRender(torch.autograd.Function):
         bg = saved[3] if ctx.has_bg else None
         params = saved[4 if ctx.has_bg else 3:]
         N, R, S = U.shape
-        eng = ctx.engine
-        if getattr(ctx.net, '_uv_engine', None) is not eng or eng._h is None:
-            eng = ctx.net._uv_grad_engine(N * R, S)
-        if any(a.data_ptr() != b.data_ptr() or a.shape != b.shape for a, b in zip(params, eng.params)):
-            raise RuntimeError("the model's parameter tensors were re-allocated between forward and backward")
-        dev = eng.dev
-        f = dict(device=dev, dtype=torch.float32)
-        dc = _grad_or_zeros(d_color, torch.empty((N, R, 3), **f))
-        dt = _grad_or_zeros(d_trans, torch.empty((N, R), **f))
-        du = None if d_uv is None else d_uv.to(dtype=torch.float32).contiguous()
-        dw = None if d_weight is None else d_weight.to(dtype=torch.float32).contiguous()
-        want = [bool(w) for w in ctx.needs_input_grad[6:]]
-        grads = eng.backward(ctx.ticket, dc, dt, du, dw, want) if eng is ctx.engine else None
-        if grads is None:           # another forward went through the engine since (or it is a new one): render this batch again, then its backward
-            *_, ticket = eng.forward(cam, rd, bg, U)
-            grads = eng.backward(ticket, dc, dt, du, dw, want)
-            if grads is None:
-                raise RuntimeError(_lib.lib().ngf_last_error().decode())
+        f = dict(device=U.device, dtype=torch.float32)      # the library reads d color and d transmittance unconditionally
+        dc = torch.zeros((N, R, 3), **f) if d_color is None else _f32(d_color)
+        dt = torch.zeros((N, R), **f) if d_trans is None else _f32(d_trans)
+        grads = replay(ctx.net, '_uv_engine', lambda: ctx.net._uv_grad_engine(N * R, S), ctx.engine, ctx.ticket, params, (cam, rd, bg, U),
+                       (dc, dt, _f32(d_uv), _f32(d_weight)), [bool(w) for w in ctx.needs_input_grad[6:]], whose="model")
         return (None,) * 6 + tuple(grads)
 
 

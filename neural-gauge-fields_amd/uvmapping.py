@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _engine, _lib
 
 
 def _seq(dims, act):
@@ -376,15 +376,7 @@ class NeuTex(nn.Module):
     # --- training (uv_train.py) ---------------------------------------------------------------------------------------------------
     def _uv_grad_engine(self, nrays, S):
         from .uv_train import UvGrad, train_params
-        e = self._uv_engine
-        if e is None or e._h is None or not e.fits(nrays, S, train_params(self)):
-            # a live engine that is too small grows to the larger of both shapes, so alternating batch shapes settle on one engine
-            old = (e.max_rays, e.max_samples) if e is not None and e._h is not None else (0, 0)
-            if e is not None:
-                e.release()
-            self._uv_engine = None
-            self._uv_engine = UvGrad(self, max(nrays, old[0]), max(S, old[1]))
-        return self._uv_engine
+        return _engine.grad_engine(self, '_uv_engine', UvGrad, train_params(self), nrays, S)
 
     @property
     def grad_engine(self):
@@ -393,9 +385,7 @@ class NeuTex(nn.Module):
 
     def release_grad_engine(self):
         """Free the training engine's per-sample buffers (the next differentiable forward builds a new one)."""
-        if self._uv_engine is not None:
-            self._uv_engine.release()
-            self._uv_engine = None
+        _engine.release_engine(self, '_uv_engine')
 
     def _train_forward(self, camera_position, ray_direction, background_color, jitter_u, template_points):
         from .uv_train import TrainOutput, _UvRender, train_params
