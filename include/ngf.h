@@ -553,6 +553,36 @@ typedef struct ngf_uvt_gemm_args {
     float *gw, *gb;
 } ngf_uvt_gemm_args;
 int ngf_debug_uvt_gemm(const ngf_uvt_gemm_args *args, void *hip_stream);
+/* test aid: ONE weight-gradient product of the InfoInv trainer on caller-owned DEVICE buffers, through the launch code the trainer's own products
+ * go through (chunk counts, grid sizes and the reduce launch are the trainer's), so that a test can compare it with fp64 at the row counts a batch
+ * never pins down.  x [m][ld] holds the delta rows and y [n][ld] the input rows, both sample-fast; `rows` sizes the launch, and with rows_dev set
+ * only min(rows, *rows_dev) rows are summed (the active count).  gw [m][n] = sum over rows of x[i][r] y[j][r], gb [m] = sum over rows of x[i][r],
+ * gw64 [m][n] = gw before its rounding to float; each may be NULL.
+ *   MFMA   ii_mm_kernel + ii_mm_reduce_kernel (the fused step): part holds ceil(rows / 8192) chunks of [m][n] doubles, partb of [m];
+ *          accumulate != 0 adds to what gw, gb and gw64 hold
+ *   FP64   ii_xty_kernel + ii_xty_reduce_kernel (the autograd path): part holds ceil(rows / 4096) chunks of [m][n + 1]; partb unused, accumulate
+ *          must be 0
+ * The call refuses (NGF_E_ARG, nothing launched) m outside 1..64, n outside 1..231, rows outside 1..2^31-1, ld < rows, and scratch of fewer than
+ * the chunks' doubles (part_elems / partb_elems).  size = sizeof(ngf_ii_product_args) as the caller sees it.  Asynchronous on hip_stream. */
+#define NGF_II_PRODUCT_MFMA 0
+#define NGF_II_PRODUCT_FP64 1
+typedef struct ngf_ii_product_args {
+    int32_t size, form;
+    int32_t m, n;
+    int32_t accumulate, pad_;
+    int64_t rows, ld;
+    const int32_t *rows_dev;        /* DEVICE, or NULL */
+    const float *x, *y;
+    double *part, *partb;
+    int64_t part_elems, partb_elems;
+    float *gw, *gb;
+    double *gw64;
+} ngf_ii_product_args;
+int ngf_debug_ii_product(const ngf_ii_product_args *args, void *hip_stream);
+/* test aid: what the InfoInv trainer's buffers hold after its last forward (of a fused step in ray chunks: after the last chunk): out[0] = the
+ * valid samples (inside the box and the alpha mask), out[1] = the active samples (weight above the threshold: the device row count of the colour
+ * products).  out is HOST memory; the call waits for hip_stream. */
+int ngf_debug_ii_counts(ngf_infoinv_trainer *t, int64_t out[2], void *hip_stream);
 
 /* test hook: the queue-position -> tile map of ngf_field_render_image evaluated on the host for `count` positions (RenderArgs::ord_*: ord_n positions
  * re-ordered, tpr tiles per image row, blocks of bw tiles x bh rows) */

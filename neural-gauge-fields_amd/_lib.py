@@ -30,7 +30,8 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_infoinv_train_step_backward", "ngf_infoinv_train_set_moments", "ngf_infoinv_train_adam_all", "ngf_infoinv_train_get_grad",
            "ngf_infoinv_train_adam_ext",
            "ngf_uv_trainer_create", "ngf_uv_trainer_destroy", "ngf_uv_trainer_bytes", "ngf_sizeof_uv_train_desc", "ngf_uv_train_forward",
-           "ngf_uv_train_backward", "ngf_uv_train_get_grads", "ngf_uv_train_params_changed", "ngf_uv_texture_eval", "ngf_debug_uvt_gemm"]
+           "ngf_uv_train_backward", "ngf_uv_train_get_grads", "ngf_uv_train_params_changed", "ngf_uv_texture_eval", "ngf_debug_uvt_gemm",
+           "ngf_debug_ii_product", "ngf_debug_ii_counts"]
 
 
 class FieldDesc(C.Structure):

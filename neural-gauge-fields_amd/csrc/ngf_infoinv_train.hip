@@ -29,6 +29,7 @@ struct ngf_infoinv_trainer {
     // the fused step (ngf_infoinv_train_step_backward / _adam_all / _adam_ext / _get_grad)
     float *f_rgb = nullptr, *f_depth = nullptr, *f_drgb = nullptr;     // [max_rays,3], [max_rays], [max_rays,3]
     double *partb = nullptr;                           // bias partials [chunks][64]
+    int64_t partb_elems = 0;
     float *exp_avg[NGF_INFOINV_TRAIN_PARAMS] = {}, *exp_avg_sq[NGF_INFOINV_TRAIN_PARAMS] = {};      // the caller's moments (set_moments)
     bool have_moments = false;
     bool have_fused = false;                           // a fused backward's gradients are in the trainer
@@ -55,18 +56,30 @@ unsigned grid_for(int64_t work, int block = 256, int64_t cap = 1 << 16)
     return (unsigned)(g < cap ? g : cap);
 }
 
-// one weight-gradient GEMM (X: M delta rows, Y: N input rows, both [k][cap]) -> gw [M][N], gb [M] (nullable), gw64 (nullable)
-int ii_xty(ngf_infoinv_trainer *t, const float *X, const float *Y, int64_t rows_cap, const int32_t *rows_dev, int M, int N, float *gw, float *gb,
+// Where one weight-gradient product reads its operands' rows and leaves its partials: the trainer fills it from its own buffers (ii_bufs),
+// ngf_debug_ii_product from its arguments.  Chunk counts, grid sizes and the reduce launch are computed in ii_xty / ii_mm, once, for both.
+struct IiProductBufs {
+    int64_t ld;                   // row stride of X and Y
+    double *part;                 // chunk partials of the matrix
+    int64_t part_elems;
+    double *partb;                // ... of the bias column (the MFMA form)
+    int64_t partb_elems;
+};
+
+// one weight-gradient GEMM (X: M delta rows, Y: N input rows, both [k][ld]) -> gw [M][N], gb [M] (nullable), gw64 (nullable)
+int ii_xty(const IiProductBufs &B, const float *X, const float *Y, int64_t rows_cap, const int32_t *rows_dev, int M, int N, float *gw, float *gb,
            double *gw64, hipStream_t st)
 {
     IiXty G{};
-    G.X = X; G.Y = Y; G.ld = t->cap; G.rows = rows_cap; G.rows_dev = rows_dev; G.M = M; G.N = N; G.NB = N + 1; G.part = t->part;
+    G.X = X; G.Y = Y; G.ld = B.ld; G.rows = rows_cap; G.rows_dev = rows_dev; G.M = M; G.N = N; G.NB = N + 1; G.part = B.part;
     const int chunks = (int)((rows_cap + kIiChunk - 1) / kIiChunk);
     const int tiles = ((M + 31) / 32) * ((N + 1 + 31) / 32);
-    if ((int64_t)chunks * M * (N + 1) > t->part_elems) return fail(NGF_E_ARG, "ngf_infoinv: GEMM partials do not fit (internal)");
+    if ((int64_t)chunks * M * (N + 1) > B.part_elems)
+        return fail(NGF_E_ARG, "ngf_infoinv: product scratch too small: part holds %lld doubles, %d chunks of %d x %d need %lld", (long long)B.part_elems,
+                    chunks, M, N + 1, (long long)chunks * M * (N + 1));
     hipLaunchKernelGGL(ii_xty_kernel, dim3(chunks > 0 ? chunks : 1, tiles), dim3(256), 0, st, G);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_xty_reduce_kernel, dim3((M * (N + 1) + 255) / 256), dim3(256), 0, st, (const double *)t->part, chunks > 0 ? chunks : 1, M, N,
+    hipLaunchKernelGGL(ii_xty_reduce_kernel, dim3((M * (N + 1) + 255) / 256), dim3(256), 0, st, (const double *)B.part, chunks > 0 ? chunks : 1, M, N,
                        gw, gb, gw64);
     HIP_TRY(hipGetLastError());
     return NGF_OK;
@@ -99,17 +112,20 @@ int ii_backward_deltas(ngf_infoinv_trainer *t, hipStream_t st)
 }
 
 // one weight-gradient product of the fused step on the matrix pipe (X: M delta rows, Y: N input rows) -> gw [M][N], gb [M], gw64 (nullable)
-int ii_mm(ngf_infoinv_trainer *t, const float *X, const float *Y, int64_t rows_cap, const int32_t *rows_dev, int M, int N, float *gw, float *gb,
+int ii_mm(const IiProductBufs &B, const float *X, const float *Y, int64_t rows_cap, const int32_t *rows_dev, int M, int N, float *gw, float *gb,
           double *gw64, bool accumulate, hipStream_t st)
 {
     IiMm G{};
-    G.X = X; G.Y = Y; G.ld = t->cap; G.rows = rows_cap; G.rows_dev = rows_dev; G.M = M; G.N = N; G.part = t->part; G.partb = t->partb;
-    const int chunks = (int)((rows_cap + kIiMmChunk - 1) / kIiMmChunk);
+    G.X = X; G.Y = Y; G.ld = B.ld; G.rows = rows_cap; G.rows_dev = rows_dev; G.M = M; G.N = N; G.part = B.part; G.partb = B.partb;
+    const int64_t chunks = (rows_cap + kIiMmChunk - 1) / kIiMmChunk;
     const int tiles = ((M + 63) / 64) * ((N + 63) / 64);
-    if ((int64_t)chunks * M * N > t->part_elems || M > kIiCH || chunks > 65535) return fail(NGF_E_ARG, "ngf_infoinv: product partials do not fit (internal)");
-    hipLaunchKernelGGL(ii_mm_kernel, dim3(tiles, chunks > 0 ? chunks : 1), dim3(256), 0, st, G);
+    if (M > kIiCH || chunks > 65535) return fail(NGF_E_ARG, "ngf_infoinv: a product of %d delta rows over %lld chunks is outside the launch", M, (long long)chunks);
+    if (chunks * M * N > B.part_elems || chunks * M > B.partb_elems)
+        return fail(NGF_E_ARG, "ngf_infoinv: product scratch too small: part / partb hold %lld / %lld doubles, %lld chunks of %d x %d need %lld / %lld",
+                    (long long)B.part_elems, (long long)B.partb_elems, (long long)chunks, M, N, (long long)(chunks * M * N), (long long)(chunks * M));
+    hipLaunchKernelGGL(ii_mm_kernel, dim3(tiles, chunks > 0 ? (unsigned)chunks : 1), dim3(256), 0, st, G);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_mm_reduce_kernel, dim3((M * N + M + 255) / 256), dim3(256), 0, st, (const double *)t->part, (const double *)t->partb, rows_cap,
+    hipLaunchKernelGGL(ii_mm_reduce_kernel, dim3((M * N + M + 255) / 256), dim3(256), 0, st, (const double *)B.part, (const double *)B.partb, rows_cap,
                        rows_dev, M, N, gw, gb, gw64, accumulate ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return NGF_OK;
@@ -157,6 +173,8 @@ int ii_adam(ngf_infoinv_trainer *t, const float *const *grad, float *const *m, f
     }
     return NGF_OK;
 }
+
+IiProductBufs ii_bufs(const ngf_infoinv_trainer *t) { return IiProductBufs{t->cap, t->part, t->part_elems, t->partb, t->partb_elems}; }
 
 }  // namespace
 
@@ -234,8 +252,9 @@ int ngf_infoinv_trainer_create(const ngf_infoinv_train_desc *desc, ngf_infoinv_t
     const int64_t chunks = (cap + kIiChunk - 1) / kIiChunk;
     t->part_elems = chunks * kIiCH * (kIiCIn + 1);
     if ((rc = t->mem.alloc(&t->part, t->part_elems))) return bail(rc);
+    t->partb_elems = ((cap + kIiMmChunk - 1) / kIiMmChunk) * kIiCH;
     if ((rc = t->mem.alloc(&t->f_rgb, 3 * nr)) || (rc = t->mem.alloc(&t->f_depth, nr)) || (rc = t->mem.alloc(&t->f_drgb, 3 * nr)) ||
-        (rc = t->mem.alloc(&t->partb, ((cap + kIiMmChunk - 1) / kIiMmChunk) * kIiCH)))
+        (rc = t->mem.alloc(&t->partb, t->partb_elems)))
         return bail(rc);
     for (int k = 0; k < NGF_INFOINV_TRAIN_PARAMS; ++k) {
         t->grad_elems[k] = ns[k];
@@ -327,12 +346,13 @@ int ngf_infoinv_train_backward_grad(ngf_infoinv_trainer *t, int64_t ticket, cons
     }
     // weight gradients (which: 3..8 density mlp.{0,2,4}.{weight,bias}, 9 basis, 10..15 rgb mlp.{0,2,4}.{weight,bias})
     const int32_t *na = A.offset + n;
-    if ((rc = ii_xty(t, A.d_d1, A.d_in, pairs, nullptr, kIiDH, kIiDIn, t->grads[3], t->grads[4], nullptr, st)) ||
-        (rc = ii_xty(t, A.d_d2, A.d_h1, pairs, nullptr, kIiDH, kIiDH, t->grads[5], t->grads[6], nullptr, st)) ||
-        (rc = ii_xty(t, A.dxs, A.d_h2, pairs, nullptr, 1, kIiDH, t->grads[7], t->grads[8], nullptr, st)) ||
-        (rc = ii_xty(t, A.c_d1, A.c_in, pairs, na, kIiCH, kIiCIn, nullptr, t->grads[11], t->m64, st)) ||
-        (rc = ii_xty(t, A.c_d2, A.c_h1, pairs, na, kIiCH, kIiCH, t->grads[12], t->grads[13], nullptr, st)) ||
-        (rc = ii_xty(t, A.c_d3, A.c_h2, pairs, na, 3, kIiCH, t->grads[14], t->grads[15], nullptr, st)))
+    const IiProductBufs B = ii_bufs(t);
+    if ((rc = ii_xty(B, A.d_d1, A.d_in, pairs, nullptr, kIiDH, kIiDIn, t->grads[3], t->grads[4], nullptr, st)) ||
+        (rc = ii_xty(B, A.d_d2, A.d_h1, pairs, nullptr, kIiDH, kIiDH, t->grads[5], t->grads[6], nullptr, st)) ||
+        (rc = ii_xty(B, A.dxs, A.d_h2, pairs, nullptr, 1, kIiDH, t->grads[7], t->grads[8], nullptr, st)) ||
+        (rc = ii_xty(B, A.c_d1, A.c_in, pairs, na, kIiCH, kIiCIn, nullptr, t->grads[11], t->m64, st)) ||
+        (rc = ii_xty(B, A.c_d2, A.c_h1, pairs, na, kIiCH, kIiCH, t->grads[12], t->grads[13], nullptr, st)) ||
+        (rc = ii_xty(B, A.c_d3, A.c_h2, pairs, na, 3, kIiCH, t->grads[14], t->grads[15], nullptr, st)))
         return rc;
     hipLaunchKernelGGL(ii_unfold_kernel, dim3((kIiCF * kIiCF + 255) / 256), dim3(256), 0, st, (const double *)t->m64, A.basis, A.w1, t->grads[10],
                        t->grads[9]);
@@ -400,12 +420,13 @@ int ngf_infoinv_train_step_backward(ngf_infoinv_trainer *t, const float *rays, c
             }
         const int64_t pairs = nc * (int64_t)n_samples;
         const int32_t *na = A.offset + nc;
-        if ((rc = ii_mm(t, A.d_d1, A.d_in, pairs, nullptr, kIiDH, kIiDIn, t->grads[3], t->grads[4], nullptr, acc, st)) ||
-            (rc = ii_mm(t, A.d_d2, A.d_h1, pairs, nullptr, kIiDH, kIiDH, t->grads[5], t->grads[6], nullptr, acc, st)) ||
-            (rc = ii_mm(t, A.dxs, A.d_h2, pairs, nullptr, 1, kIiDH, t->grads[7], t->grads[8], nullptr, acc, st)) ||
-            (rc = ii_mm(t, A.c_d1, A.c_in, pairs, na, kIiCH, kIiCIn, nullptr, t->grads[11], t->m64, acc, st)) ||
-            (rc = ii_mm(t, A.c_d2, A.c_h1, pairs, na, kIiCH, kIiCH, t->grads[12], t->grads[13], nullptr, acc, st)) ||
-            (rc = ii_mm(t, A.c_d3, A.c_h2, pairs, na, 3, kIiCH, t->grads[14], t->grads[15], nullptr, acc, st)))
+        const IiProductBufs B = ii_bufs(t);
+        if ((rc = ii_mm(B, A.d_d1, A.d_in, pairs, nullptr, kIiDH, kIiDIn, t->grads[3], t->grads[4], nullptr, acc, st)) ||
+            (rc = ii_mm(B, A.d_d2, A.d_h1, pairs, nullptr, kIiDH, kIiDH, t->grads[5], t->grads[6], nullptr, acc, st)) ||
+            (rc = ii_mm(B, A.dxs, A.d_h2, pairs, nullptr, 1, kIiDH, t->grads[7], t->grads[8], nullptr, acc, st)) ||
+            (rc = ii_mm(B, A.c_d1, A.c_in, pairs, na, kIiCH, kIiCIn, nullptr, t->grads[11], t->m64, acc, st)) ||
+            (rc = ii_mm(B, A.c_d2, A.c_h1, pairs, na, kIiCH, kIiCH, t->grads[12], t->grads[13], nullptr, acc, st)) ||
+            (rc = ii_mm(B, A.c_d3, A.c_h2, pairs, na, 3, kIiCH, t->grads[14], t->grads[15], nullptr, acc, st)))
             return rc;
     }
     hipLaunchKernelGGL(ii_unfold_kernel, dim3((kIiCF * kIiCF + 255) / 256), dim3(256), 0, st, (const double *)t->m64, A.basis, A.w1, t->grads[10],
@@ -452,6 +473,54 @@ int ngf_infoinv_train_adam_ext(ngf_infoinv_trainer *t, const float *const grad[N
     if (!t || !grad || !exp_avg || !exp_avg_sq || !step_count || !lr) return fail(NGF_E_ARG, "ngf_infoinv_train_adam_ext: null argument");
     DeviceScope ds(t->device);
     return ii_adam(t, grad, exp_avg, exp_avg_sq, step_count, lr, beta1, beta2, eps, 0.0f, (hipStream_t)hip_stream);
+}
+
+// test aid (include/ngf.h): the valid and the active count of the rays the trainer's buffers hold
+int ngf_debug_ii_counts(ngf_infoinv_trainer *t, int64_t out[2], void *hip_stream)
+{
+    if (!t || !out) return fail(NGF_E_ARG, "ngf_debug_ii_counts: null argument");
+    const IiArgs &A = t->A;
+    if (A.n <= 0 || A.S <= 0) return fail(NGF_E_ARG, "ngf_debug_ii_counts: no forward yet");
+    hipStream_t st = (hipStream_t)hip_stream;
+    DeviceScope ds(t->device);
+    const size_t pairs = (size_t)A.n * (size_t)A.S;
+    uint8_t *host = (uint8_t *)malloc(pairs);
+    if (!host) return fail(NGF_E_HIP, "ngf_debug_ii_counts: out of host memory");
+    int32_t active = 0;
+    if (hipMemcpyAsync(host, A.valid, pairs, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&active, A.offset + A.n, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        free(host);
+        return fail(NGF_E_HIP, "ngf_debug_ii_counts: copy to the host failed");
+    }
+    int64_t valid = 0;
+    for (size_t i = 0; i < pairs; ++i) valid += host[i] ? 1 : 0;
+    free(host);
+    out[0] = valid;
+    out[1] = active;
+    return NGF_OK;
+}
+
+// test aid (include/ngf.h): one weight-gradient product on caller-owned buffers through the trainer's own launch code
+int ngf_debug_ii_product(const ngf_ii_product_args *a, void *hip_stream)
+{
+    if (!a) return fail(NGF_E_ARG, "ngf_debug_ii_product: null argument");
+    if (a->size != (int32_t)sizeof(ngf_ii_product_args)) return fail(NGF_E_ARG, "ngf_debug_ii_product: ngf_ii_product_args layout mismatch");
+    if (a->m <= 0 || a->m > kIiCH || a->n <= 0 || a->n > kIiCIn)
+        return fail(NGF_E_ARG, "ngf_debug_ii_product: m = %d, n = %d outside 1..%d x 1..%d", a->m, a->n, kIiCH, kIiCIn);
+    if (a->rows <= 0 || a->rows >= (1ll << 31) || a->ld < a->rows)
+        return fail(NGF_E_ARG, "ngf_debug_ii_product: rows = %lld must be in 1..2^31-1 and ld = %lld at least rows", (long long)a->rows, (long long)a->ld);
+    if (!a->x || !a->y || !a->part) return fail(NGF_E_ARG, "ngf_debug_ii_product: x, y and part must not be NULL");
+    const IiProductBufs B{a->ld, a->part, a->part_elems, a->partb, a->partb ? a->partb_elems : 0};
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (a->form == NGF_II_PRODUCT_MFMA) {
+        if (!a->partb) return fail(NGF_E_ARG, "ngf_debug_ii_product: the MFMA form needs partb");
+        return ii_mm(B, a->x, a->y, a->rows, a->rows_dev, a->m, a->n, a->gw, a->gb, a->gw64, a->accumulate != 0, st);
+    }
+    if (a->form == NGF_II_PRODUCT_FP64) {
+        if (a->accumulate) return fail(NGF_E_ARG, "ngf_debug_ii_product: the fp64 form does not accumulate");
+        return ii_xty(B, a->x, a->y, a->rows, a->rows_dev, a->m, a->n, a->gw, a->gb, a->gw64, st);
+    }
+    return fail(NGF_E_ARG, "ngf_debug_ii_product: unknown form %d", a->form);
 }
 
 }  // extern "C"

@@ -633,7 +633,7 @@ __global__ void __launch_bounds__(256) ii_plane_grad_kernel(const unsigned long 
 
 // ---- 9. weight gradients: part[chunk][m][n] = sum over the chunk's rows of X[m][row] * Y[n][row]  (column N = 1: the bias) ---------------
 // 256 threads own a 32 x 32 output tile (4 outputs each), rows go through LDS 64 at a time; fp64 accumulation.  rows_dev != NULL: the row
-// count is *rows_dev (the active count, read on the device).
+// count is min(rows, *rows_dev) (the active count, read on the device).
 struct IiXty {
     const float *X, *Y;
     int64_t ld;                   // row stride of both (the buffers' capacity)
@@ -647,7 +647,7 @@ __global__ void __launch_bounds__(256) ii_xty_kernel(const IiXty G)
 {
     __shared__ float xs[64][33];
     __shared__ float ys[64][33];
-    const int64_t rows = G.rows_dev ? (int64_t)*G.rows_dev : G.rows;
+    const int64_t rows = G.rows_dev ? min(G.rows, (int64_t)*G.rows_dev) : G.rows;          // never past the launch, as ii_mm_kernel
     const int tiles_n = (G.NB + 31) / 32;
     const int tm = blockIdx.y / tiles_n, tn = blockIdx.y - tm * tiles_n;
     const int64_t r0 = (int64_t)blockIdx.x * kIiChunk;

@@ -41,9 +41,39 @@ class InfoInvTrainDesc(C.Structure):
     ]
 
 
+class IiProductArgs(C.Structure):
+    """ngf_ii_product_args (include/ngf.h): one weight-gradient product of the trainer on caller-owned buffers, a test aid."""
+    _fields_ = [("size", C.c_int32), ("form", C.c_int32), ("m", C.c_int32), ("n", C.c_int32), ("accumulate", C.c_int32), ("pad_", C.c_int32),
+                ("rows", C.c_int64), ("ld", C.c_int64), ("rows_dev", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
+                ("part", C.c_void_p), ("partb", C.c_void_p), ("part_elems", C.c_int64), ("partb_elems", C.c_int64),
+                ("gw", C.c_void_p), ("gb", C.c_void_p), ("gw64", C.c_void_p)]
+
+
+PRODUCT_MFMA, PRODUCT_FP64 = 0, 1
+
+
+def debug_product(form, stream=None, **kw):
+    """ngf_debug_ii_product: keyword = field of IiProductArgs; a torch tensor is passed as its data pointer (``part`` / ``partb`` also set
+    their element counts).  Returns the library's return code: 0, or 1 with ngf_last_error() set."""
+    L = _lib.lib()
+    _bind(L)
+    a = IiProductArgs()
+    a.size, a.form = C.sizeof(IiProductArgs), int(form)
+    for k, v in kw.items():
+        if isinstance(v, torch.Tensor):
+            if k in ("part", "partb"):
+                setattr(a, k + "_elems", v.numel())
+            v = v.data_ptr()
+        setattr(a, k, v)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    return L.ngf_debug_ii_product(C.byref(a), C.c_void_p(st))
+
+
 def _bind(L):
     if getattr(L, "_ngf_infoinv_bound", False):
         return
+    L.ngf_debug_ii_product.argtypes = [C.POINTER(IiProductArgs), C.c_void_p]
+    L.ngf_debug_ii_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
     L.ngf_infoinv_trainer_create.argtypes = [C.POINTER(InfoInvTrainDesc), C.POINTER(C.c_void_p), C.c_void_p]
     L.ngf_infoinv_trainer_destroy.argtypes = [C.c_void_p]
     L.ngf_infoinv_trainer_bytes.argtypes = [C.c_void_p]
@@ -140,6 +170,13 @@ class InfoInvGrad(GradEngine):
             _lib.check(self.L.ngf_infoinv_train_forward(self._h, rays.data_ptr(), jitter.data_ptr(), n, int(S), int(bool(white_bg)),
                                                         int(bool(infoinv)), rgb.data_ptr(), depth.data_ptr(), C.byref(ticket), st))
         return rgb, depth, int(ticket.value)
+
+    def counts(self):
+        """(valid samples, active samples) of the rays the engine's buffers hold (ngf_debug_ii_counts, a test aid; waits for the stream)."""
+        out = (C.c_int64 * 2)()
+        with on_stream(self.dev) as st:
+            _lib.check(self.L.ngf_debug_ii_counts(self._h, out, st))
+        return int(out[0]), int(out[1])
 
     def backward(self, ticket, d_rgb, want):
         """``want[k]``: return parameter k's gradient (else None).  None = the ticket is stale (another forward used the buffers)."""
