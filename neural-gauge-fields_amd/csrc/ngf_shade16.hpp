@@ -85,6 +85,15 @@ __device__ __forceinline__ void mlp_tail16(const float *blob, int oW2, int oB2, 
 #ifdef NGF_EXP_NO_LAYER2      // TIMING EXPERIMENT (wrong pixels): a sixteenth of layer 2's matrix instructions -- what the matrix pipe's share of the pass costs
 #pragma unroll
     for (int t = 0; t < 16; ++t) c[t & 3] = NGF_MFMA16(w2[((t & 3) * 16 + t) * 64], h[t], c[t & 3]);
+#elif defined(NGF_EXP_W2_NOWAIT)   // TIMING EXPERIMENT (wrong pixels): the 64 matrix instructions of layer 2 on eight A operands read once in front of the block -- what the LDS waits inside it cost
+    float wr[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wr[k] = w2[k * 64];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 16; ++t)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) c[mt] = NGF_MFMA16(wr[(4 * t + mt) & 7], h[t], c[mt]);
 #else
 #pragma unroll
     for (int t = 0; t < 16; ++t)
@@ -535,10 +544,30 @@ __device__ __forceinline__ BilPk baked16_cell(const float rec[kRecFloats], int P
     return bp;
 }
 
-__device__ __forceinline__ void baked16q_issue(const float rec[kRecFloats], int st, int kq, BakedQuarter &g, const RecCells *cells)
+// What a stage needs of its plane's descriptor when the cell comes from the record.  TEX: when it is read from the kernel-argument segment --
+//   0  by every stage (24 s_load and twelve s_waitcnt lgkmcnt(0) per pass, each in front of the stage's four loads)
+//   1  by a plane's FIRST stage, kept in SGPRs for that plane's four stages (three round trips per pass, nothing new lives across the march loop)
+//   2  all three planes at the top of the pass: one round trip, beside the wait for the pass's queue records (nine SGPRs for the gather block) -- the default
+// Same addresses either way.  Without record cells (the kernels without 12-float records) a stage reads the whole descriptor, as before.
+struct TexRef { decltype(Tex::p) p; decltype(Tex::stride) stride; };
+
+__device__ __forceinline__ TexRef karg_texref(int P)
+{
+    const Tex t = karg_tex(offsetof(RenderArgs, app) + P * sizeof(Tex));
+    return TexRef{t.p, t.stride};
+}
+
+template <int TEX>
+__device__ __forceinline__ void baked16q_issue(const float rec[kRecFloats], int st, int kq, BakedQuarter &g, const RecCells *cells, TexRef (&tx)[3])
 {
     const int P = st >> 2, mt = st & 3;
-    const Tex t = karg_tex(offsetof(RenderArgs, app) + P * sizeof(Tex));
+    Tex t;
+    if (TEX == 0 || !cells) t = karg_tex(offsetof(RenderArgs, app) + P * sizeof(Tex));
+    else {
+        if (TEX == 1 && mt == 0) tx[P] = karg_texref(P);
+        t = Tex{};
+        t.p = tx[P].p; t.stride = tx[P].stride;
+    }
     const int32_t idx = cells ? cells->idx[P] : baked16_cell(rec, P, t, cells).idx;
     const f32x4 *t00 = tex_at<f32x4>(t.p, (uint32_t)idx * 64u + 4u * (kq + 4 * mt));
     const f32x4 *t01 = tex_at<f32x4>(t.p, (uint32_t)(idx + t.stride) * 64u + 4u * (kq + 4 * mt));
@@ -573,9 +602,9 @@ __device__ __forceinline__ BakedQuarter &baked16q_buffer(BakedQuarter &g0, Baked
     else if constexpr (ST % NB == 1) return g1;
     else return g2;
 }
-template <int NB, int... ST>
+template <int NB, int TEX, int... ST>
 __device__ __forceinline__ void baked16q_stages(const float rg[kRecFloats], int kqg, BakedQuarter &g0, BakedQuarter &g1, BakedQuarter &g2, f32x2 sum[8],
-                                                const RecCells *gcells, std::integer_sequence<int, ST...>)
+                                                const RecCells *gcells, TexRef (&tx)[3], std::integer_sequence<int, ST...>)
 {
     f32x2 wa = {0.0f, 0.0f}, wb = {0.0f, 0.0f};
     auto stage = [&](auto st_) {
@@ -584,14 +613,14 @@ __device__ __forceinline__ void baked16q_stages(const float rg[kRecFloats], int 
         baked16q_consume(rg, st, g, wa, wb, sum, gcells);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (st + NB < 12) {
-            baked16q_issue(rg, st + NB, kqg, g, gcells);
+            baked16q_issue<TEX>(rg, st + NB, kqg, g, gcells, tx);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
     (stage(std::integral_constant<int, ST>{}), ...);
 }
 
-template <typename L, int NB = 2>
+template <typename L, int NB = 2, int TEX = 0>
 __device__ __forceinline__ void baked16_layer1_quarters(const RenderArgs &A, const float *blob, const float rec[kRecFloats], const f32x4 v,
                                                         int lane, f32x4 acc[4], const float *pre, const RecCells *gcells)
 {
@@ -607,17 +636,22 @@ __device__ __forceinline__ void baked16_layer1_quarters(const RenderArgs &A, con
 #pragma unroll
         for (int k = 2; k < kRecFloats; ++k) rg[k] = 0.0f;
     }
+    TexRef tx[3] = {};
+    if (TEX == 2 && gcells) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) tx[p] = karg_texref(p);
+    }
     BakedQuarter g0, g1, g2;
-    baked16q_issue(rg, 0, kqg, g0, gcells);
+    baked16q_issue<TEX>(rg, 0, kqg, g0, gcells, tx);
     __builtin_amdgcn_sched_barrier(0);
-    baked16q_issue(rg, 1, kqg, g1, gcells);
+    baked16q_issue<TEX>(rg, 1, kqg, g1, gcells, tx);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (NB == 3) {
-        baked16q_issue(rg, 2, kqg, g2, gcells);
+        baked16q_issue<TEX>(rg, 2, kqg, g2, gcells, tx);
         __builtin_amdgcn_sched_barrier(0);
     }
     f32x2 sum[8];
-    baked16q_stages<NB>(rg, kqg, g0, g1, g2, sum, gcells, std::make_integer_sequence<int, 12>{});
+    baked16q_stages<NB, TEX>(rg, kqg, g0, g1, g2, sum, gcells, tx, std::make_integer_sequence<int, 12>{});
     const int src = 4 * (lane & 15) + kq;
     const float *b0 = pre ? pre + kq * 16 : blob + L::B1 + kq * 16;
 #pragma unroll
@@ -633,7 +667,14 @@ __device__ __forceinline__ void baked16_layer1_quarters(const RenderArgs &A, con
     }
 }
 
-// QUARTER: the sixteen-wave policy's front part (quarter-plane stages); every other kernel keeps the half-plane form and its instruction stream
+// A/B builds (profiles/r12_pass_feed.txt): -DNGF_W16_TEX=0 gives the sixteen-wave pass a descriptor read per stage (the form before), 1 one per plane
+// in front of the plane's first stage; NGF_EXP_TEX_ONCE is the name under which mode 2 was measured as a bound before it was built
+#ifndef NGF_W16_TEX
+#define NGF_W16_TEX 2
+#endif
+
+// QUARTER: the sixteen-wave policy's front part (quarter-plane stages, the three planes' descriptors read once at the top of the pass); every other
+// kernel keeps the half-plane form and its instruction stream
 template <bool QUARTER = false>
 __device__ __forceinline__ void mlp_pass16_baked(const RenderArgs &A, const float *blob, const float rec[kRecFloats], const f32x4 v,
                                                  int lane, float rgb[3], const float *pre = nullptr, const RecCells *gcells = nullptr)
@@ -641,7 +682,7 @@ __device__ __forceinline__ void mlp_pass16_baked(const RenderArgs &A, const floa
     using L = MlpLayout16Baked;
     blob = per_pass16(blob);
     f32x4 acc[4];
-    if constexpr (QUARTER) baked16_layer1_quarters<L, NGF_W16_STAGES>(A, blob, rec, v, lane, acc, pre, gcells);
+    if constexpr (QUARTER) baked16_layer1_quarters<L, NGF_W16_STAGES, NGF_W16_TEX>(A, blob, rec, v, lane, acc, pre, gcells);
     else baked16_layer1<L>(A, blob, rec, v, lane, acc, pre, gcells);
     mlp_tail16(blob, L::W2, L::B2, L::W3, L::B3, lane, acc, rgb);
 }
