@@ -588,6 +588,34 @@ int ngf_debug_ii_counts(ngf_infoinv_trainer *t, int64_t out[2], void *hip_stream
  * re-ordered, tpr tiles per image row, blocks of bw tiles x bh rows) */
 int ngf_debug_tile_order(const uint32_t *q, int64_t count, uint32_t ord_n, uint32_t tpr, uint32_t bw, uint32_t bh, uint32_t *out);
 
+/* ---- Mesh export: marching cubes over a dense float volume on the device -----------------------------------------
+ * The volume is [dims[0], dims[1], dims[2]] = [gx,gy,gz] floats on the DEVICE, element (i,j,k) at vol[i * strides[0] + j * strides[1] + k * strides[2]]
+ * (element strides; none may be zero), so getDenseAlpha's x-major tensor and updateAlphaMask's [gz,gy,gx] one both go in as they are.  A lattice
+ * point is inside iff v >= level (NaN: outside); point (i,j,k) owns its +x, +y, +z edges and an owned edge carries a vertex iff its endpoints
+ * differ, at t = (level - v_a) / (v_b - v_a) from the owner a (t = 0.5 unless 0 <= t <= 1), position origin + ((float)index + t) * spacing per axis.
+ *
+ * count : fills the workspace (at least what ngf_mesh_workspace_bytes returns; at most 8 bytes per lattice point from 64 points on, below 512 bytes under that)
+ *         and writes {vertices, triangles} to counts_dev (DEVICE int64[2]) on the stream.  A dimension of 1 means no cells: zero counts, no error.
+ * emit  : nv / nt are the two counts (the caller sized the outputs by them): when they are not what count left in the workspace -- or the
+ *         workspace holds the count of other dims / another level -- the call returns NGF_E_ARG and writes nothing.  It waits for the stream once
+ *         to read them back.  vertices [nv,3] float in lattice-point order (k fastest), a point's edges in x, y, z order; faces [nt,3] int32 in cell
+ *         order then table order, normals pointing to the outside (low) side, NGF_MESH_FLIP reverses each triangle; with NGF_MESH_NORMALS
+ *         normals [nv,3]: central differences (one-sided at the border) at the edge's two lattice points, interpolated with t, negated,
+ *         normalised, (0,0,0) for a zero or non-finite gradient.  The output is a function of the volume alone: two calls are bit-identical.
+ * Both refuse (NGF_E_ARG, before touching a GPU, ngf_last_error names the function) null pointers, a dimension below 1, a zero stride, a
+ * non-finite level, a workspace that is too small, unknown flag bits and nv / nt outside 0..3n / 0..5n; volumes of 3 * gx * gy * gz >= 2^31
+ * are NGF_E_UNSUPPORTED and their workspace size is -1.  No kernel of the unit waits for another workgroup. */
+enum { NGF_MESH_FLIP = 1, NGF_MESH_NORMALS = 2 };
+int64_t ngf_mesh_workspace_bytes(int32_t gx, int32_t gy, int32_t gz);
+int ngf_mesh_count(const float *vol, const int32_t *dims, const int64_t *strides, float level, void *workspace, int64_t workspace_bytes,
+                   int64_t *counts_dev, void *hip_stream);
+int ngf_mesh_emit(const float *vol, const int32_t *dims, const int64_t *strides, float level, const float *origin, const float *spacing, int32_t flags,
+                  const void *workspace, int64_t workspace_bytes, int64_t nv, int64_t nt, float *vertices, float *normals, int32_t *faces,
+                  void *hip_stream);
+/* test hook: the unit's device-wide exclusive scan alone, in place on n pairs of uint32 (DEVICE); scratch holds the upper levels' chunk totals
+ * (n / 512 + 8 pairs are enough); the two totals go to totals_dev (DEVICE int64[2]) */
+int ngf_debug_mesh_scan(uint32_t *pairs, int64_t n, uint32_t *scratch, int64_t scratch_pairs, int64_t *totals_dev, void *hip_stream);
+
 const char *ngf_last_error(void);
 int ngf_abi_version(void);
 /* sizeof(ngf_field_desc) as compiled into the library (binding self-check) */

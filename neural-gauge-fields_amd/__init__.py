@@ -3,7 +3,7 @@
 
 Sub-modules: ``triplane`` / ``infoinv`` / ``uvmapping`` (drop-in field modules over the HIP C-ABI), ``fieldbase``
 (shared Base + renderer), ``geometry`` (init_para scalars), ``opt`` (config_parser), ``rays`` (on-device ray
-generation), ``dist`` (ray-sharded multi-GPU render), ``synth`` (seeded inputs), ``_lib`` (ctypes binding of
-libngf_hip.so).
+generation), ``dist`` (ray-sharded multi-GPU render), ``synth`` (seeded inputs), ``mesh`` (marching cubes on the device,
+PLY export; ``mesh_table`` derives its case table), ``_lib`` (ctypes binding of libngf_hip.so).
 """
-__all__ = ["triplane", "infoinv", "uvmapping", "fieldbase", "geometry", "opt", "rays", "dist", "synth", "cases"]
+__all__ = ["triplane", "infoinv", "uvmapping", "fieldbase", "geometry", "opt", "rays", "dist", "synth", "cases", "mesh", "mesh_table"]

@@ -31,7 +31,8 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_infoinv_train_adam_ext",
            "ngf_uv_trainer_create", "ngf_uv_trainer_destroy", "ngf_uv_trainer_bytes", "ngf_sizeof_uv_train_desc", "ngf_uv_train_forward",
            "ngf_uv_train_backward", "ngf_uv_train_get_grads", "ngf_uv_train_params_changed", "ngf_uv_texture_eval", "ngf_debug_uvt_gemm",
-           "ngf_debug_ii_product", "ngf_debug_ii_counts"]
+           "ngf_debug_ii_product", "ngf_debug_ii_counts",
+           "ngf_mesh_workspace_bytes", "ngf_mesh_count", "ngf_mesh_emit", "ngf_debug_mesh_scan"]
 
 
 class FieldDesc(C.Structure):
@@ -59,6 +60,7 @@ class UvDesc(C.Structure):
 
 UV_F_SPLIT_BF16 = 1
 UV_TEX_DIFFUSE = 1          # ngf_uv_texture_eval flags
+MESH_FLIP, MESH_NORMALS = 1, 2      # ngf_mesh_emit flags
 
 
 def build(force: bool = False) -> str:
@@ -136,6 +138,12 @@ def _load(path):
         L.ngf_planes_l1.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngf_planes_l1_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngf_debug_tile_order.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.ngf_mesh_workspace_bytes.restype = C.c_int64
+        L.ngf_mesh_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        L.ngf_mesh_count.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.ngf_mesh_emit.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32,
+                                    C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ngf_debug_mesh_scan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         if L.ngf_abi_version() != 5 or L.ngf_sizeof_field_desc() != C.sizeof(FieldDesc):
             raise RuntimeError("libngf_hip.so ABI mismatch (version or ngf_field_desc layout)")
         _LIBS[path] = L

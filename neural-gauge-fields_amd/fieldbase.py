@@ -372,6 +372,23 @@ class Base(torch.nn.Module):
         return new_aabb
 
     @torch.no_grad()
+    def export_mesh(self, path=None, level=0.005, gridSize=None, normals=False, flip=False, **kw):
+        """The reference's --export_mesh (TriPlane/main.py:400-401, whose mesh(args) is not defined there): getDenseAlpha(gridSize, **kw) -- InfoInv's
+        infoinv= passes through -- then marching cubes at ``level`` on the device (ngf_amd.mesh), with the vertices on the lattice the alpha
+        was sampled on, aabb[0] + index * (aabb[1] - aabb[0]) / (n - 1).  Returns (verts, faces[, normals]) as device tensors and writes a binary
+        PLY when ``path`` is given."""
+        from . import mesh
+        if torch.device(self.device).type != 'cuda':
+            raise RuntimeError("ngf_amd fields export meshes on the GPU only (device='cuda'); there is no CPU path")
+        alpha, _ = self.getDenseAlpha(gridSize, **kw)
+        lo, hi = np.asarray(self._aabb_host(), dtype=np.float32).reshape(2, 3)
+        steps = np.maximum(np.asarray(alpha.shape, dtype=np.float32) - np.float32(1), np.float32(1))
+        out = mesh.marching_cubes(alpha, level, spacing=(hi - lo) / steps, origin=lo, normals=normals, flip=flip)
+        if path is not None:
+            mesh.write_ply(path, out[0].cpu().numpy(), out[1].cpu().numpy())
+        return out
+
+    @torch.no_grad()
     def filtering_rays(self, all_rays, all_rgbs, N_samples=256, chunk=10240 * 5, bbox_only=False):
         """FieldBase.py:218-246: drop rays that miss the box (bbox_only) or never touch an occupied voxel."""
         dev = torch.device(self.device)
