@@ -146,6 +146,27 @@ int ngf_field_march(const ngf_field *f, const float *rays, int64_t n, int32_t n_
  *                          the n_samples points of ray i samples the alpha mask > 0 (requires a mask). */
 int ngf_field_alpha(const ngf_field *f, const float *xyz, int64_t n, int32_t mode, float length, float *alpha,
                     void *hip_stream);
+/* Point queries (additive to ABI 5): what the reference's module answers with compute_gauge / compute_density / compute_rgb (TriPlane/models/
+ * Field.py:53-105), for n world-space points xyz [n,3] in one launch.  All pointers are device pointers.  Each output may be NULL (not wanted); at
+ * least one must be given.  mode as in ngf_field_render.  Asynchronous on the stream; n == 0 returns NGF_OK.  Not differentiable.
+ *   dirs    view directions, used as given (NOT normalised, like compute_rgb(..., view_sampled)): [n,3] with dir_stride 3, or ONE direction [3] shared
+ *           by every point with dir_stride 0.  Required when rgb is wanted, ignored otherwise.
+ *   flags   NGF_QUERY_NO_MASK: sigma ignores the field's alpha mask.
+ * A point is in the box when aabb[0] <= p <= aabb[1] holds in every component (sample_ray's test, FieldBase.py:134; a NaN component is outside).
+ *   coords [n,6] = compute_gauge(normalize_coord(xyz), mode) as (t_xy, t_yz, t_xz) for in-box points; InfoInv: its `transform` (the identity split).
+ *                  The alpha mask does not apply.  Points outside the box get 0.
+ *   sigma  [n]   = feature2density(compute_density(coords)) for in-box points.  With an alpha mask and without NGF_QUERY_NO_MASK it is 0 where
+ *                  sample_alpha is not > 0 (as Base.forward, FieldBase.py:261-267).  0 outside the box.
+ *   rgb    [n,3] = sigmoid(rgb_decoder(compute_rgb(coords), dir)) for in-box points.  Neither the alpha mask nor any weight threshold applies.
+ *                  0 outside the box.
+ * Outside points never reach a texture: whatever they hold (NaN, +-inf, 3e38), their lanes continue with the box centre and store exact zeros.
+ * A point's outputs depend on that point and the handle alone, bit for bit -- not on n, its position in the batch or the other points.
+ * NGF_E_ARG (before any GPU work): null f or xyz, n < 0, dir_stride outside {0, 3}, unknown flag bits, rgb without dirs, no output at all. */
+enum { NGF_QUERY_NO_MASK = 1 };
+int ngf_field_query(const ngf_field *f, const float *xyz, int64_t n, int32_t mode, const float *dirs,
+                    int32_t dir_stride /* 0: one shared direction, 3: one per point */, int32_t flags, float *sigma /*[n]*/,
+                    float *rgb /*[n,3]*/, float *coords /*[n,6]*/, void *hip_stream);
+
 /* Replaces: getDenseAlpha + updateAlphaMask (FieldBase.py:161-216) in one pass over the [gx,gy,gz] lattice of the aabb:
  * sx/sy/sz = the three torch.linspace(0,1,g) vectors (device), mode as ngf_field_alpha, length = stepSize, thres =
  * alphaMask_thres.  Outputs (device): alpha_zyx [gz,gy,gx] (dense alpha, transposed like FieldBase.py:185), volume_zyx

@@ -32,7 +32,8 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_uv_trainer_create", "ngf_uv_trainer_destroy", "ngf_uv_trainer_bytes", "ngf_sizeof_uv_train_desc", "ngf_uv_train_forward",
            "ngf_uv_train_backward", "ngf_uv_train_get_grads", "ngf_uv_train_params_changed", "ngf_uv_texture_eval", "ngf_debug_uvt_gemm",
            "ngf_debug_ii_product", "ngf_debug_ii_counts",
-           "ngf_mesh_workspace_bytes", "ngf_mesh_count", "ngf_mesh_emit", "ngf_debug_mesh_scan"]
+           "ngf_mesh_workspace_bytes", "ngf_mesh_count", "ngf_mesh_emit", "ngf_debug_mesh_scan",
+           "ngf_field_query"]
 
 
 class FieldDesc(C.Structure):
@@ -61,6 +62,7 @@ class UvDesc(C.Structure):
 UV_F_SPLIT_BF16 = 1
 UV_TEX_DIFFUSE = 1          # ngf_uv_texture_eval flags
 MESH_FLIP, MESH_NORMALS = 1, 2      # ngf_mesh_emit flags
+QUERY_NO_MASK = 1                   # ngf_field_query flags
 
 
 def build(force: bool = False) -> str:
@@ -102,6 +104,8 @@ def _load(path):
         L.ngf_generate_rays_dtu.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                             C.c_void_p]
         L.ngf_field_alpha.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+        L.ngf_field_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
         L.ngf_field_alpha_mask_build.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                                  C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngf_field_ray_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]

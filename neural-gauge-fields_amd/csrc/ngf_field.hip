@@ -12,6 +12,7 @@
 #include "ngf_pack.hpp"
 #include "ngf_render.hpp"
 #include "ngf_alpha.hpp"
+#include "ngf_query.hpp"
 #ifdef NGF_EXPERIMENTS      // libngf_hip_exp.so only (make: second target): kernels that were built, measured and lost -- specialised march / shade
                             // waves, LDS-staged texture strips -- and the tuning variants (8 / 16 waves, two steps per lane, section profile).  The
                             // product library carries only kernels that can be the default; the experiment tests load the other one.
@@ -1147,6 +1148,69 @@ extern "C" int ngf_field_alpha(const ngf_field *f, const float *xyz, int64_t n, 
     if (n < 0) return fail(NGF_E_ARG, "ngf_field_alpha: n=%lld", (long long)n);
     if (n == 0) return NGF_OK;
     return launch_alpha(f, xyz, Lattice{nullptr, nullptr, nullptr, 0, 0, 0}, n, mode, length, alpha, (hipStream_t)hip_stream);
+}
+
+// ---- ngf_field_query: density, colour and plane coordinates at world-space points (ngf_query.hpp) ------------------------------------------------
+template <typename PD, typename PC>
+static int launch_query_kernel(const ngf_field *f, const RenderArgs &A, const QueryArgs &Q, hipStream_t st)
+{
+    constexpr bool COLOUR = !std::is_same_v<PC, NoColour>;
+    const bool staged = COLOUR || (PD::INFOINV && Q.sigma);          // the kernel's own condition: a coords-only InfoInv call stages nothing
+    const size_t lds = staged ? ((size_t)((A.blob_floats + 3) & ~3) + (COLOUR ? 4 * kQueryViewFloats : 0)) * sizeof(float) : 0;
+    // the grid-stride loop and its cap follow launch_alpha (8 workgroups per CU; one where the MLP image is staged) and, with a colour stage,
+    // ngf_field_decode_rgb (4 per CU)
+    int64_t grid = (Q.n + 255) / 256;
+    const int64_t cap = (COLOUR ? 4 : staged ? 1 : 8) * (int64_t)f->num_cus;
+    if (grid > cap) grid = cap;
+    if (knob(KNOB_GRID) > 0 && grid > knob(KNOB_GRID)) grid = knob(KNOB_GRID);      // tests: fewer workgroups -> every wave takes many tiles
+    if (lds) HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(query_kernel<PD, PC>), lds));
+    hipLaunchKernelGGL((query_kernel<PD, PC>), dim3((unsigned)grid), dim3(256), lds, st, A, Q);
+    HIP_TRY(hipGetLastError());
+    return NGF_OK;
+}
+
+// the colour side as ngf_field_decode_rgb picks it (BD: the handle has NGF_F_BAKE_DENSITY, which NGF_F_NO_FOLD excludes and level 3's bf16 pass requires)
+template <typename PD, bool BD>
+static int launch_query_triplane(const ngf_field *f, const RenderArgs &A, const QueryArgs &Q, hipStream_t st)
+{
+    if (!Q.rgb) return launch_query_kernel<PD, NoColour>(f, A, Q, st);
+    if constexpr (!BD) {
+        if (f->flags & NGF_F_NO_FOLD) return launch_query_kernel<PD, TriPlaneNoFoldPolicy>(f, A, Q, st);
+    } else {
+        if ((f->flags & NGF_F_SPLIT_BF16) && (f->flags & NGF_F_BAKE_COLOR)) return launch_query_kernel<PD, TriPlaneBakedBf16Policy>(f, A, Q, st);
+    }
+    if (f->flags & NGF_F_SPLIT_BF16) return launch_query_kernel<PD, TriPlaneBf16Policy<false, 8>>(f, A, Q, st);
+    if (f->flags & NGF_F_BAKE_COLOR) return launch_query_kernel<PD, TriPlanePolicy<false, true, 8, 1>>(f, A, Q, st);
+    return launch_query_kernel<PD, TriPlanePolicy<false, false, 8, 1>>(f, A, Q, st);
+}
+
+extern "C" int ngf_field_query(const ngf_field *f, const float *xyz, int64_t n, int32_t mode, const float *dirs, int32_t dir_stride, int32_t flags,
+                               float *sigma, float *rgb, float *coords, void *hip_stream)
+{
+    if (!f || !xyz) return fail(NGF_E_ARG, "ngf_field_query: null argument");
+    if (n < 0) return fail(NGF_E_ARG, "ngf_field_query: n=%lld", (long long)n);
+    if (dir_stride != 0 && dir_stride != 3) return fail(NGF_E_ARG, "ngf_field_query: dir_stride=%d (0: one shared direction, 3: one per point)", dir_stride);
+    if (flags & ~NGF_QUERY_NO_MASK) return fail(NGF_E_ARG, "ngf_field_query: unknown flags 0x%x", (unsigned)flags);
+    if (rgb && !dirs) return fail(NGF_E_ARG, "ngf_field_query: rgb needs dirs");
+    if (!sigma && !rgb && !coords) return fail(NGF_E_ARG, "ngf_field_query: no output requested");
+    if (n == 0) return NGF_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    field_use(f, st);
+    RenderArgs A = f->proto;
+    A.mode = mode ? 1 : 0;
+    const QueryArgs Q{xyz, rgb ? dirs : nullptr, n, dir_stride, (flags & NGF_QUERY_NO_MASK) ? 0 : 1, sigma, rgb, coords};
+    if (int rc = poison_lds(st)) return rc;
+    // the density side as launch_alpha picks it
+    if (f->model == NGF_MODEL_INFOINV) {
+        if (f->flags & NGF_F_SPLIT_BF16)
+            return rgb ? launch_query_kernel<InfoInvSplitPolicy, InfoInvSplitPolicy>(f, A, Q, st) : launch_query_kernel<InfoInvSplitPolicy, NoColour>(f, A, Q, st);
+        return rgb ? launch_query_kernel<InfoInvPolicy, InfoInvPolicy>(f, A, Q, st) : launch_query_kernel<InfoInvPolicy, NoColour>(f, A, Q, st);
+    }
+    if (f->flags & NGF_F_BAKE_DENSITY) {
+        if (A.gauge_same) return launch_query_triplane<TriPlanePolicy<true, false, 8, 1>, true>(f, A, Q, st);
+        return launch_query_triplane<GaugeAny<TriPlanePolicy<true, false, 8, 1>>, true>(f, A, Q, st);
+    }
+    return launch_query_triplane<TriPlanePolicy<false, false, 8, 1>, false>(f, A, Q, st);
 }
 
 extern "C" int ngf_field_alpha_mask_build(const ngf_field *f, int32_t mode, const float *sx, const float *sy, const float *sz, int32_t gx, int32_t gy,

@@ -371,21 +371,96 @@ class Base(torch.nn.Module):
         self._handle_key = None
         return new_aabb
 
+    def _query_mode(self, **kw) -> int:
+        raise NotImplementedError
+
     @torch.no_grad()
-    def export_mesh(self, path=None, level=0.005, gridSize=None, normals=False, flip=False, **kw):
+    def query(self, xyz, viewdirs=None, *, use_mask=True, want_coords=False, **kw):
+        """Density, colour and gauge-shifted plane coordinates at world-space points ``xyz`` [..., 3] in one launch (ngf_field_query): what the
+        reference's module answers with compute_gauge / compute_density / compute_rgb (TriPlane/models/Field.py:53-105).
+
+        ``viewdirs`` is [..., 3] like ``xyz`` or a single 3-vector shared by every point; directions are used as given, not normalised.  ``kw`` is
+        ``iteration=0`` for TriPlane (forward's rule, the gauge is applied iff iteration >= gauge_start) and ``infoinv=True`` for InfoInv.
+        Returns a dict: ``'sigma'`` [...] (feature2density of the density; 0 outside the aabb and, with an alpha mask and ``use_mask``, where the
+        mask is empty), ``'rgb'`` [..., 3] when ``viewdirs`` is given (sigmoid of the decoder's output; no mask, no weight threshold; 0 outside the
+        aabb) and ``'coords'`` [..., 6] = (t_xy, t_yz, t_xz) with ``want_coords`` (0 outside the aabb).  Runs under ``torch.no_grad()``: the
+        result is NOT differentiable.  GPU only."""
+        mode = self._query_mode(**kw)
+        dev = torch.device(self.device)
+        if dev.type != 'cuda':
+            raise RuntimeError("ngf_amd fields answer queries on the GPU only (device='cuda'); there is no CPU path")
+        if xyz.shape[-1] != 3:
+            raise ValueError(f"xyz must be [..., 3], got {tuple(xyz.shape)}")
+        shape = tuple(xyz.shape[:-1])
+        pts = xyz.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        n = pts.shape[0]
+        dirs, stride = None, 0
+        if viewdirs is not None:
+            dirs = torch.as_tensor(viewdirs).to(device=dev, dtype=torch.float32)
+            if tuple(dirs.shape) == (3,) and shape != ():
+                stride = 0                       # one direction for every point
+            elif tuple(dirs.shape) == shape + (3,):
+                stride = 3
+            else:
+                raise ValueError(f"viewdirs must be {shape + (3,)} like xyz or a single 3-vector, got {tuple(dirs.shape)}")
+            dirs = dirs.reshape(-1, 3).contiguous()
+        out = {'sigma': torch.empty((n,), device=dev, dtype=torch.float32)}
+        if dirs is not None:
+            out['rgb'] = torch.empty((n, 3), device=dev, dtype=torch.float32)
+        if want_coords:
+            out['coords'] = torch.empty((n, 6), device=dev, dtype=torch.float32)
+        if n:
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().ngf_field_query(
+                    self.handle(), pts.data_ptr(), n, int(mode), None if dirs is None else dirs.data_ptr(), stride,
+                    0 if use_mask else _lib.QUERY_NO_MASK, out['sigma'].data_ptr(), out['rgb'].data_ptr() if dirs is not None else None,
+                    out['coords'].data_ptr() if want_coords else None, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return {k: v.view(shape + tuple(v.shape[1:])) for k, v in out.items()}
+
+    @torch.no_grad()
+    def export_mesh(self, path=None, level=0.005, gridSize=None, normals=False, flip=False, colors=None, color_kw=None, **kw):
         """The reference's --export_mesh (TriPlane/main.py:400-401, whose mesh(args) is not defined there): getDenseAlpha(gridSize, **kw) -- InfoInv's
         infoinv= passes through -- then marching cubes at ``level`` on the device (ngf_amd.mesh), with the vertices on the lattice the alpha
         was sampled on, aabb[0] + index * (aabb[1] - aabb[0]) / (n - 1).  Returns (verts, faces[, normals]) as device tensors and writes a binary
-        PLY when ``path`` is given."""
+        PLY when ``path`` is given.
+
+        ``colors``: None (no colours: the call above), True (every vertex is seen along ``-normal``; the vertex normals are computed whether or
+        not they are returned, and a zero normal gives the direction (0, 0, -1)) or one direction ``(dx, dy, dz)`` shared by all vertices.  The
+        colours are ``query(verts, dirs, **color_kw)['rgb']`` through ``evalout.to_uint8`` (clamp, times 255, truncate); ``color_kw`` defaults to
+        ``kw`` for InfoInv (``infoinv=`` reaches the alpha and the colour alike) and to ``{}`` for TriPlane.  They come back as a uint8 [nv, 3]
+        device tensor, the LAST element of the returned tuple, and go into the PLY as ``red green blue`` (with the normals when ``normals``)."""
         from . import mesh
         if torch.device(self.device).type != 'cuda':
             raise RuntimeError("ngf_amd fields export meshes on the GPU only (device='cuda'); there is no CPU path")
         alpha, _ = self.getDenseAlpha(gridSize, **kw)
         lo, hi = np.asarray(self._aabb_host(), dtype=np.float32).reshape(2, 3)
         steps = np.maximum(np.asarray(alpha.shape, dtype=np.float32) - np.float32(1), np.float32(1))
-        out = mesh.marching_cubes(alpha, level, spacing=(hi - lo) / steps, origin=lo, normals=normals, flip=flip)
+        if colors is None:
+            out = mesh.marching_cubes(alpha, level, spacing=(hi - lo) / steps, origin=lo, normals=normals, flip=flip)
+            if path is not None:
+                mesh.write_ply(path, out[0].cpu().numpy(), out[1].cpu().numpy())
+            return out
+        from . import evalout
+        by_normal = colors is True
+        res = mesh.marching_cubes(alpha, level, spacing=(hi - lo) / steps, origin=lo, normals=normals or by_normal, flip=flip)
+        verts, faces = res[0], res[1]
+        if by_normal:
+            zero = (res[2] == 0).all(dim=-1, keepdim=True)
+            dirs = torch.where(zero, torch.tensor([0.0, 0.0, -1.0], device=verts.device), -res[2])
+        else:
+            dirs = torch.tensor([float(c) for c in colors], dtype=torch.float32)
+            if tuple(dirs.shape) != (3,):
+                raise ValueError("colors must be None, True or one direction (dx, dy, dz)")
+        if color_kw is None:
+            color_kw = dict(kw) if self.MODEL == _lib.MODEL_INFOINV else {}
+        if verts.shape[0]:
+            rgb8 = evalout.to_uint8(self.query(verts, dirs, **color_kw)['rgb'])
+        else:
+            rgb8 = torch.empty((0, 3), device=verts.device, dtype=torch.uint8)
+        out = (verts, faces, res[2], rgb8) if normals else (verts, faces, rgb8)
         if path is not None:
-            mesh.write_ply(path, out[0].cpu().numpy(), out[1].cpu().numpy())
+            mesh.write_ply(path, verts.cpu().numpy(), faces.cpu().numpy(), normals=res[2].cpu().numpy() if normals else None,
+                           colors=rgb8.cpu().numpy())
         return out
 
     @torch.no_grad()

@@ -46,6 +46,10 @@ class TriPlane(Base):
         """compute_alpha / getDenseAlpha / updateAlphaMask(..., infoinv=True) of InfoInv/models/FieldBase.py:140,161,180."""
         return int(bool(infoinv))
 
+    def _query_mode(self, infoinv=True) -> int:
+        """Kernel mode of ``query``: the infoinv= switch of compute_density / compute_rgb (InfoInv/models/Field.py:63,83)."""
+        return int(bool(infoinv))
+
     def density_L1(self):
         """InfoInv/models/Field.py:107-110: mean|plane_xy| + mean|plane_yz| + mean|plane_xz|, differentiable.  On the device ngf_planes_l1 /
         ngf_planes_l1_backward (triplane._DensityL1, any plane size); anything else is the reference's torch expression."""

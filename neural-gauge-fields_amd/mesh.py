@@ -56,19 +56,41 @@ def marching_cubes(volume, level, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0
     return (verts, faces, nrm) if normals else (verts, faces)
 
 
-def write_ply(path, verts, faces):
-    """Binary little-endian PLY: vertex ``x y z`` as float32, face ``vertex_indices`` as a list (uchar count) of int32."""
+def write_ply(path, verts, faces, normals=None, colors=None):
+    """Binary little-endian PLY: vertex ``x y z [nx ny nz] [red green blue]`` -- the floats first (float32), then the uchar colours -- and face
+    ``vertex_indices`` as a list (uchar count) of int32.  ``normals`` [nv,3] float and ``colors`` [nv,3] uint8 are optional; without them the
+    file is the plain ``x y z`` one."""
     v = np.ascontiguousarray(np.asarray(verts, dtype='<f4').reshape(-1, 3))
     f = np.asarray(faces, dtype='<i4').reshape(-1, 3)
     rec = np.empty((f.shape[0],), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
     rec['n'] = 3
     rec['i'] = f
+    props = "property float x\nproperty float y\nproperty float z\n"
+    fields = [('p', '<f4', (3,))]
+    if normals is not None:
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+        fields.append(('n', '<f4', (3,)))
+    if colors is not None:
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        fields.append(('c', 'u1', (3,)))
+    vrec = np.empty((v.shape[0],), dtype=fields)          # packed: 12 [+ 12] [+ 3] bytes per vertex
+    vrec['p'] = v
+    if normals is not None:
+        nn = np.asarray(normals, dtype='<f4').reshape(-1, 3)
+        if nn.shape != v.shape:
+            raise ValueError(f"write_ply: normals {nn.shape} do not match the {v.shape[0]} vertices")
+        vrec['n'] = nn
+    if colors is not None:
+        cc = np.asarray(colors)
+        if cc.dtype != np.uint8 or cc.reshape(-1, 3).shape != v.shape:
+            raise ValueError(f"write_ply: colors must be uint8 [{v.shape[0]},3], got {cc.dtype} {cc.shape}")
+        vrec['c'] = cc.reshape(-1, 3)
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {v.shape[0]}\n" + props +
               f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, 'wb') as fh:
         fh.write(header.encode('ascii'))
-        fh.write(v.tobytes())
+        fh.write(vrec.tobytes())
         fh.write(rec.tobytes())
 
 

@@ -116,6 +116,10 @@ class TriPlane(Base):
             d.gauge_h[k], d.gauge_w[k] = g.shape[2], g.shape[3]
         d.dens_w1, d.dens_b1 = dp(self.density_decoder.weight), dp(self.density_decoder.bias)
 
+    def _query_mode(self, iteration=0) -> int:
+        """Kernel mode of ``query``: forward's rule, the gauge is applied iff iteration >= gauge_start (Field.py:58)."""
+        return int(iteration >= self.gauge_start)
+
     def forward(self, rays_chunk, white_bg=True, is_train=False, N_samples=-1, iteration=0, collect_stats=False, out=None, jitter=None, coin=None, row_width=0):
         """FieldBase.py:251: gauge is applied iff iteration >= gauge_start (Field.py:58).  With ``is_train=True``, autograd enabled and
         parameters that require gradients -- the reference's training loop, TriPlane/main.py:272 -- the result is differentiable with respect to
