@@ -333,6 +333,22 @@ int ngf_train_params_changed(ngf_trainer *t);
  * waves) to 8 counters; with bit 1 << 21 the backward kernels count their atomic line transactions (counters 8, 9) and the
  * scatter calls that took the per-tap path (10).  This reads and clears them (out16: 16 x uint64, host).  Synchronises. */
 int ngf_train_debug_sections(ngf_trainer *t, uint64_t *out16);
+/* test aid (additive to ABI 5): the four weight-gradient products of one chunk of the TriPlane trainer on caller-owned DEVICE buffers, through the
+ * set-up and launch code of the trainer's own step (xty_all_kernel: at most two workgroups per CU walk the 32-row k-chunks), so that a test can
+ * compare them with fp64 at row counts and values a batch never pins down.  The operands are sample-major as the colour backward leaves them:
+ * d1 [rows][64], d2 [rows][64], d3 [rows][16] (columns 0..2 used), f [rows][144], h1 [rows][64], h2 [rows][64], v [rows][16] (columns 0..14
+ * used).  `rows` sizes the launch, and with rows_dev set only min(rows, *rows_dev) rows are summed (the active count).  The outputs are ADDED to,
+ * as in the step: m [64][144] += d1^T f, gw2 [64][64] += d2^T h1, gw1 [64][159], columns 144..158 only, += d1^T v, gw3 [3][64] += d3^T h2.
+ * The call refuses (NGF_E_ARG, nothing launched) a NULL operand or output, an operand that is not 16-byte aligned, rows outside 1..2^31-1 and
+ * size != sizeof(ngf_train_xty_args) as the caller sees it.  Asynchronous on hip_stream. */
+typedef struct ngf_train_xty_args {
+    int32_t size, pad_;
+    int64_t rows;
+    const int32_t *rows_dev;        /* DEVICE, or NULL */
+    const float *d1, *d2, *d3, *f, *h1, *h2, *v;
+    float *m, *gw2, *gw1, *gw3;
+} ngf_train_xty_args;
+int ngf_debug_train_xty(const ngf_train_xty_args *args, void *hip_stream);
 
 /* ---- the InfoInv tree's training step: InfoInv/main.py:262-330 -------------------------------------------------------------------
  * Replaces field(rays_train, is_train=True, infoinv=...) (InfoInv/models/FieldBase.py:228-282) under autograd and its backward, for a

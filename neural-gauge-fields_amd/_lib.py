@@ -24,7 +24,7 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_uv_create", "ngf_uv_destroy", "ngf_uv_render", "ngf_uv_render_batch", "ngf_field_alpha", "ngf_field_ray_filter",
            "ngf_eval_workspace_bytes", "ngf_eval_frame_u8", "ngf_eval_depth_range", "ngf_eval_depth_colormap", "ngf_eval_mse",
            "ngf_eval_ssim", "ngf_trainer_create", "ngf_trainer_destroy", "ngf_trainer_bytes", "ngf_sizeof_train_desc", "ngf_train_backward", "ngf_train_backward2",
-           "ngf_train_forward", "ngf_train_backward_grad", "ngf_train_get_grad", "ngf_train_get_active", "ngf_train_overflow_count", "ngf_train_adam", "ngf_train_adam_all", "ngf_train_adam_ext", "ngf_train_get_grads", "ngf_train_params_changed", "ngf_train_debug_sections", "ngf_resize_bilinear", "ngf_uv_set_texture", "ngf_uv_texture_edit", "ngf_field_alpha_mask_build", "ngf_pack_mask_bits", "ngf_debug_set", "ngf_debug_get", "ngf_debug_dirty_lds", "ngf_debug_xcd_histogram", "ngf_debug_tile_plan", "ngf_debug_packed_plane_floats", "ngf_debug_tile_order", "ngf_planes_l1", "ngf_planes_l1_backward", "ngf_pool_trim", "ngf_pool_set_limit", "ngf_pool_bytes",
+           "ngf_train_forward", "ngf_train_backward_grad", "ngf_train_get_grad", "ngf_train_get_active", "ngf_train_overflow_count", "ngf_train_adam", "ngf_train_adam_all", "ngf_train_adam_ext", "ngf_train_get_grads", "ngf_train_params_changed", "ngf_train_debug_sections", "ngf_debug_train_xty", "ngf_resize_bilinear", "ngf_uv_set_texture", "ngf_uv_texture_edit", "ngf_field_alpha_mask_build", "ngf_pack_mask_bits", "ngf_debug_set", "ngf_debug_get", "ngf_debug_dirty_lds", "ngf_debug_xcd_histogram", "ngf_debug_tile_plan", "ngf_debug_packed_plane_floats", "ngf_debug_tile_order", "ngf_planes_l1", "ngf_planes_l1_backward", "ngf_pool_trim", "ngf_pool_set_limit", "ngf_pool_bytes",
            "ngf_infoinv_trainer_create", "ngf_infoinv_trainer_destroy", "ngf_infoinv_trainer_bytes", "ngf_sizeof_infoinv_train_desc",
            "ngf_infoinv_train_forward", "ngf_infoinv_train_backward_grad", "ngf_infoinv_train_get_grads", "ngf_infoinv_train_params_changed",
            "ngf_infoinv_train_step_backward", "ngf_infoinv_train_set_moments", "ngf_infoinv_train_adam_all", "ngf_infoinv_train_get_grad",

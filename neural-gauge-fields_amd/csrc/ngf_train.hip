@@ -351,6 +351,43 @@ static int train_forward_part(ngf_trainer *t, const float *rays, const float *ji
     return NGF_OK;
 }
 
+// The four weight-gradient products of one chunk of activation rows, one launch: the step's own call and ngf_debug_train_xty (a test aid)
+// both go through here.  gw1 is the whole [64][159] tensor: the product writes its 15 view columns.
+static void launch_xty(int num_cus, const float *D1, const float *D2, const float *D3, const float *F, const float *H1, const float *H2,
+                       const float *V, float *M, float *gw2, float *gw1, float *gw3, int rows, const int32_t *rows_dev, hipStream_t sx)
+{
+    int xg = (rows + 31) / 32;                      // 32-sample chunks; at most two workgroups per CU walk them
+    if (xg > 2 * num_cus) xg = 2 * num_cus;
+    // heaviest first: M = Delta1^T F (train_unfold_kernel turns it into d W1[:, :144] and d basis), d W2, the 15 view columns of d W1, d W3
+    XtyAll G;
+    G.X[0] = D1; G.ldx[0] = 64; G.Y[0] = F;  G.ldy[0] = 144; G.mvalid[0] = 64; G.nvalid[0] = 144; G.out[0] = M; G.ldo[0] = 144;
+    G.X[1] = D2; G.ldx[1] = 64; G.Y[1] = H1; G.ldy[1] = 64;  G.mvalid[1] = 64; G.nvalid[1] = 64;  G.out[1] = gw2; G.ldo[1] = 64;
+    G.X[2] = D1; G.ldx[2] = 64; G.Y[2] = V;  G.ldy[2] = 16;  G.mvalid[2] = 64; G.nvalid[2] = 15;  G.out[2] = gw1 + 144; G.ldo[2] = 159;
+    G.X[3] = D3; G.ldx[3] = 16; G.Y[3] = H2; G.ldy[3] = 64;  G.mvalid[3] = 3;  G.nvalid[3] = 64;  G.out[3] = gw3; G.ldo[3] = 64;
+    G.rows = rows; G.rows_dev = rows_dev;
+    hipLaunchKernelGGL(xty_all_kernel, dim3(xg, 4), dim3(256), 0, sx, G);
+}
+
+extern "C" int ngf_debug_train_xty(const ngf_train_xty_args *a, void *hip_stream)
+{
+    if (!a) return fail(NGF_E_ARG, "ngf_debug_train_xty: null argument");
+    if (a->size != (int32_t)sizeof(ngf_train_xty_args)) return fail(NGF_E_ARG, "ngf_debug_train_xty: ngf_train_xty_args layout mismatch");
+    if (a->rows < 1 || a->rows > INT32_MAX) return fail(NGF_E_ARG, "ngf_debug_train_xty: rows = %lld must be in 1..2^31-1", (long long)a->rows);
+    const float *in[7] = {a->d1, a->d2, a->d3, a->f, a->h1, a->h2, a->v};
+    for (int k = 0; k < 7; ++k) {
+        if (!in[k]) return fail(NGF_E_ARG, "ngf_debug_train_xty: operand %d is NULL", k);
+        if (reinterpret_cast<uintptr_t>(in[k]) & 15) return fail(NGF_E_ARG, "ngf_debug_train_xty: operand %d is not 16-byte aligned", k);
+    }
+    if (!a->m || !a->gw2 || !a->gw1 || !a->gw3) return fail(NGF_E_ARG, "ngf_debug_train_xty: m, gw2, gw1 and gw3 must not be NULL");
+    int dev = 0, num_cus = 256;
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDevice(&dev));
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess) num_cus = prop.multiProcessorCount;
+    launch_xty(num_cus, a->d1, a->d2, a->d3, a->f, a->h1, a->h2, a->v, a->m, a->gw2, a->gw1, a->gw3, (int)a->rows, a->rows_dev, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return NGF_OK;
+}
+
 static inline dim3 comp_grid(int64_t n) { return dim3((unsigned)((n + 64 / kCompLanes - 1) / (64 / kCompLanes))); }
 
 // Part B; the compositing kernel of the calling form has run on hip_stream.  rgb_loss may be NULL (no loss is delivered).
@@ -416,17 +453,7 @@ static int train_backward_part(ngf_trainer *t, ngf_trainer::Pending &P, double *
             const int gx = (int)std::min<int64_t>((items + 255) / 256, (int64_t)64 * t->num_cus);
             hipLaunchKernelGGL(train_bin_gather_kernel, dim3(gx, 3), dim3(256), 0, sb, T);
         }
-        const int rows = T.chunk_n;
-        int xg = (rows + 31) / 32;                      // 32-sample chunks; at most two workgroups per CU walk them
-        if (xg > 2 * t->num_cus) xg = 2 * t->num_cus;
-        // heaviest first: M = Delta1^T F (train_unfold_kernel turns it into d W1[:, :144] and d basis), d W2, the 15 view columns of d W1, d W3
-        XtyAll G;
-        G.X[0] = T.D1; G.ldx[0] = 64; G.Y[0] = T.F;  G.ldy[0] = 144; G.mvalid[0] = 64; G.nvalid[0] = 144; G.out[0] = T.M; G.ldo[0] = 144;
-        G.X[1] = T.D2; G.ldx[1] = 64; G.Y[1] = T.H1; G.ldy[1] = 64;  G.mvalid[1] = 64; G.nvalid[1] = 64;  G.out[1] = t->g_dense[TP_W2]; G.ldo[1] = 64;
-        G.X[2] = T.D1; G.ldx[2] = 64; G.Y[2] = T.V;  G.ldy[2] = 16;  G.mvalid[2] = 64; G.nvalid[2] = 15;  G.out[2] = t->g_dense[TP_W1] + 144; G.ldo[2] = 159;
-        G.X[3] = T.D3; G.ldx[3] = 16; G.Y[3] = T.H2; G.ldy[3] = 64;  G.mvalid[3] = 3;  G.nvalid[3] = 64;  G.out[3] = t->g_dense[TP_W3]; G.ldo[3] = 64;
-        G.rows = rows; G.rows_dev = cnt;
-        hipLaunchKernelGGL(xty_all_kernel, dim3(xg, 4), dim3(256), 0, sx, G);
+        launch_xty(t->num_cus, T.D1, T.D2, T.D3, T.F, T.H1, T.H2, T.V, T.M, t->g_dense[TP_W2], t->g_dense[TP_W1], t->g_dense[TP_W3], T.chunk_n, cnt, sx);
         if (base + t->chunk >= list_len) hipLaunchKernelGGL(train_unfold_kernel, dim3(96), dim3(256), 0, sx, T, t->g_dense[TP_W1], t->g_dense[TP_BASIS]);
         if (fork) {
             // both events are recorded before an error can return: the wrapper's rescue join waits on events of THIS step

@@ -41,6 +41,26 @@ class TrainDesc(C.Structure):
     ]
 
 
+class TrainXtyArgs(C.Structure):
+    """ngf_train_xty_args (include/ngf.h): the four weight-gradient products of one chunk on caller-owned buffers, a test aid."""
+    _fields_ = [("size", C.c_int32), ("pad_", C.c_int32), ("rows", C.c_int64), ("rows_dev", C.c_void_p),
+                ("d1", C.c_void_p), ("d2", C.c_void_p), ("d3", C.c_void_p), ("f", C.c_void_p), ("h1", C.c_void_p), ("h2", C.c_void_p),
+                ("v", C.c_void_p), ("m", C.c_void_p), ("gw2", C.c_void_p), ("gw1", C.c_void_p), ("gw3", C.c_void_p)]
+
+
+def debug_xty(stream=None, **kw):
+    """ngf_debug_train_xty: keyword = field of TrainXtyArgs; a torch tensor is passed as its data pointer.  ``stream``: a HIP stream handle
+    (default: torch's current stream).  Returns the library's return code: 0, or 1 with ngf_last_error() set."""
+    L = _lib.lib()
+    L.ngf_debug_train_xty.argtypes = [C.POINTER(TrainXtyArgs), C.c_void_p]
+    a = TrainXtyArgs()
+    a.size = C.sizeof(TrainXtyArgs)
+    for k, v in kw.items():
+        setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    return L.ngf_debug_train_xty(C.byref(a), C.c_void_p(st))
+
+
 def _bind(L):
     if getattr(L, "_ngf_train_bound", False):
         return
