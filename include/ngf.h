@@ -307,7 +307,9 @@ int ngf_train_get_grad(ngf_trainer *t, int32_t which, float *out, void *hip_stre
 int ngf_train_adam(ngf_trainer *t, int32_t which, int32_t step_count, float lr, float beta1, float beta2, float eps,
                    float l1_weight, void *hip_stream);
 /* optimizer.step() for all 15 parameters: step_count[k] >= 1 updates parameter k with lr[k], step_count[k] <= 0 skips it (a
- * parameter whose .grad is None).  The six plane updates are one launch each, the nine MLP parameters share one. */
+ * parameter whose .grad is None).  The six plane updates are one launch each, the nine MLP parameters share one.  What
+ * ngf_train_adam would refuse for any of them (a trainer without moments; a plane whose packed copy is stale after
+ * ngf_train_params_changed) is refused before anything is launched: NGF_E_ARG, and no parameter or moment has changed. */
 int ngf_train_adam_all(ngf_trainer *t, const int32_t step_count[NGF_TRAIN_PARAMS], const float lr[NGF_TRAIN_PARAMS], float beta1,
                        float beta2, float eps, float l1_weight, void *hip_stream);
 /* ABI 5 -- the two calls behind the reference's own loop on the drop-in field (TriPlane/main.py:234-242,294-302: torch's loss, total_loss.backward(),

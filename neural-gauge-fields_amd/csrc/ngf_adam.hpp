@@ -62,4 +62,26 @@ __global__ void __launch_bounds__(256) adam_dense_all_kernel(const AdamDense<N> 
     }
 }
 
+// The host side of that launch, for every trainer: tensor j (parameter p[j], moments m[j] / v[j], gradient g[j], count[j] elements, its own
+// step count and learning rate) takes part when on(j); the others become empty segments.  Returns the launch error (no launch when nothing is on).
+template <int N, typename On>
+inline hipError_t adam_dense_all(float *const *p, float *const *m, float *const *v, const float *const *g, const int64_t *count,
+                                 const int32_t *step_count, const float *lr, float beta1, float beta2, float eps, On on, const int32_t *skip,
+                                 hipStream_t st)
+{
+    AdamDense<N> D;
+    int32_t at = 0;
+    for (int j = 0; j < N; ++j) {
+        D.p[j] = p[j]; D.m[j] = m[j]; D.v[j] = v[j]; D.g[j] = g[j];
+        D.begin[j] = at;
+        D.a[j] = adam_args(step_count[j] > 0 ? step_count[j] : 1, lr[j], beta1, beta2, eps, 0.0f);      // step 1 for an empty segment: never read
+        if (on(j)) at += (int32_t)count[j];
+    }
+    D.begin[N] = at;
+    D.skip = skip;
+    if (at <= 0) return hipSuccess;
+    hipLaunchKernelGGL(adam_dense_all_kernel<N>, dim3((at + 255) / 256), dim3(256), 0, st, D);
+    return hipGetLastError();
+}
+
 }  // namespace ngf

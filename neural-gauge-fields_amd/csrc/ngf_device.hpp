@@ -501,4 +501,31 @@ __device__ __forceinline__ float softplus_shift(float f)
 // feed the next layer's B operand directly -- no transposition or cross-lane traffic between layers.
 __device__ __forceinline__ int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
+// Exclusive prefix of count[0..n) -> offset[0..n) by ONE block of 1024 threads (sh: 1024 ints of its LDS): every thread sums a run of consecutive
+// counts, one scan runs over the 1024 run sums, then the run is written (scanning chunk after chunk of 1024 took 80 barriers for a 4096-ray
+// batch, 10 us).  Returns the inclusive sum of the thread's run: in thread 1023 the total.  The trainers' scan kernels (train_prefix_kernel,
+// ii_prefix_kernel, uvt_scan_kernel) are this call and what each does with the total.
+__device__ __forceinline__ int32_t block_scan_runs(const int32_t *count, int64_t n, int32_t *offset, int32_t *sh)
+{
+    const int t = threadIdx.x;
+    const int64_t per = (n + 1023) / 1024;
+    const int64_t b0 = t * per, b1 = b0 + per < n ? b0 + per : n;
+    int32_t c = 0;
+    for (int64_t b = b0; b < b1; ++b) c += count[b];
+    sh[t] = c;
+    __syncthreads();
+    for (int s = 1; s < 1024; s <<= 1) {
+        const int32_t add = t >= s ? sh[t - s] : 0;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    int32_t run = sh[t] - c;
+    for (int64_t b = b0; b < b1; ++b) {
+        offset[b] = run;
+        run += count[b];
+    }
+    return sh[t];
+}
+
 }  // namespace ngf

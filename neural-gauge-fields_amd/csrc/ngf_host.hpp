@@ -1,5 +1,6 @@
 // ngf_host.hpp -- what the host-side translation units of libngf_hip.so share: the thread-local error slot behind
-// ngf_last_error(), the HIP_TRY early-return macro, launch-grid helpers.
+// ngf_last_error(), the HIP_TRY early-return macro, NGF_LAUNCH (a kernel launch whose launch error returns the same way), the device
+// scope and the allocation list of a trainer handle.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,6 +45,14 @@ int poison_alloc(void *p, size_t bytes, hipStream_t st);     // no-op unless kno
     do {                                                                                                     \
         hipError_t e_ = (expr);                                                                              \
         if (e_ != hipSuccess) return ngf::fail(NGF_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));    \
+    } while (0)
+
+// A checked launch: hipLaunchKernelGGL, then the launch error (bad configuration, too much LDS, a missing code object) returns like any
+// other HIP error.  A kernel with template arguments goes in parentheses: NGF_LAUNCH((kernel<A, B>), grid, block, lds, stream, args...).
+#define NGF_LAUNCH(kernel, grid, block, lds, stream, ...)                                                    \
+    do {                                                                                                     \
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                   \
+        HIP_TRY(hipGetLastError());                                                                          \
     } while (0)
 
 namespace ngf {

@@ -77,11 +77,9 @@ int ii_xty(const IiProductBufs &B, const float *X, const float *Y, int64_t rows_
     if ((int64_t)chunks * M * (N + 1) > B.part_elems)
         return fail(NGF_E_ARG, "ngf_infoinv: product scratch too small: part holds %lld doubles, %d chunks of %d x %d need %lld", (long long)B.part_elems,
                     chunks, M, N + 1, (long long)chunks * M * (N + 1));
-    hipLaunchKernelGGL(ii_xty_kernel, dim3(chunks > 0 ? chunks : 1, tiles), dim3(256), 0, st, G);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_xty_reduce_kernel, dim3((M * (N + 1) + 255) / 256), dim3(256), 0, st, (const double *)B.part, chunks > 0 ? chunks : 1, M, N,
-                       gw, gb, gw64);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(ii_xty_kernel, dim3(chunks > 0 ? chunks : 1, tiles), dim3(256), 0, st, G);
+    NGF_LAUNCH(ii_xty_reduce_kernel, dim3((M * (N + 1) + 255) / 256), dim3(256), 0, st, (const double *)B.part, chunks > 0 ? chunks : 1, M, N, gw, gb,
+               gw64);
     return NGF_OK;
 }
 
@@ -91,23 +89,16 @@ int ii_backward_deltas(ngf_infoinv_trainer *t, hipStream_t st)
     IiArgs &A = t->A;
     const int64_t n = A.n, pairs = n * (int64_t)A.S;
     const unsigned rg = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ii_composite_bwd_kernel, dim3(rg), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_color_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_density_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(ii_composite_bwd_kernel, dim3(rg), dim3(256), 0, st, A);
+    NGF_LAUNCH(ii_color_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
+    NGF_LAUNCH(ii_density_bwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
     // plane gradients: bound -> scale -> fixed-point scatter
-    hipLaunchKernelGGL(ii_bound_kernel, dim3(kIiBoundBlocks), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_scale_kernel, dim3(1), dim3(64), 0, st, A);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(ii_bound_kernel, dim3(kIiBoundBlocks), dim3(256), 0, st, A);
+    NGF_LAUNCH(ii_scale_kernel, dim3(1), dim3(64), 0, st, A);
     for (int p = 0; p < 3; ++p)
         HIP_TRY(hipMemsetAsync(t->gacc[p], 0, (size_t)(A.tex[p].H + 2) * (A.tex[p].W + 2) * kIiC * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(ii_scatter_kernel<true>, dim3(grid_for(pairs * kIiDIn)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_scatter_kernel<false>, dim3(grid_for(pairs * kIiCF)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(ii_scatter_kernel<true>, dim3(grid_for(pairs * kIiDIn)), dim3(256), 0, st, A);
+    NGF_LAUNCH(ii_scatter_kernel<false>, dim3(grid_for(pairs * kIiCF)), dim3(256), 0, st, A);
     return NGF_OK;
 }
 
@@ -123,11 +114,9 @@ int ii_mm(const IiProductBufs &B, const float *X, const float *Y, int64_t rows_c
     if (chunks * M * N > B.part_elems || chunks * M > B.partb_elems)
         return fail(NGF_E_ARG, "ngf_infoinv: product scratch too small: part / partb hold %lld / %lld doubles, %lld chunks of %d x %d need %lld / %lld",
                     (long long)B.part_elems, (long long)B.partb_elems, (long long)chunks, M, N, (long long)(chunks * M * N), (long long)(chunks * M));
-    hipLaunchKernelGGL(ii_mm_kernel, dim3(tiles, chunks > 0 ? (unsigned)chunks : 1), dim3(256), 0, st, G);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_mm_reduce_kernel, dim3((M * N + M + 255) / 256), dim3(256), 0, st, (const double *)B.part, (const double *)B.partb, rows_cap,
-                       rows_dev, M, N, gw, gb, gw64, accumulate ? 1 : 0);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(ii_mm_kernel, dim3(tiles, chunks > 0 ? (unsigned)chunks : 1), dim3(256), 0, st, G);
+    NGF_LAUNCH(ii_mm_reduce_kernel, dim3((M * N + M + 255) / 256), dim3(256), 0, st, (const double *)B.part, (const double *)B.partb, rows_cap, rows_dev,
+               M, N, gw, gb, gw64, accumulate ? 1 : 0);
     return NGF_OK;
 }
 
@@ -149,28 +138,16 @@ int ii_adam(ngf_infoinv_trainer *t, const float *const *grad, float *const *m, f
         const dim3 g(H * ((W + 63) / 64));
         // a stale packed copy is simply rewritten; its zero border is written whenever the forward packs (t->packed unset)
         if (!grad && t->planes_fixed)
-            hipLaunchKernelGGL(ii_adam_plane_kernel<true>, g, dim3(256), 0, st, d.plane[p], m[p], v[p], H, W, (const unsigned long long *)t->gacc[p],
-                               (const double *)t->A.bound, (const float *)nullptr, t->tex[p], a);
+            NGF_LAUNCH(ii_adam_plane_kernel<true>, g, dim3(256), 0, st, d.plane[p], m[p], v[p], H, W, (const unsigned long long *)t->gacc[p],
+                       (const double *)t->A.bound, (const float *)nullptr, t->tex[p], a);
         else
-            hipLaunchKernelGGL(ii_adam_plane_kernel<false>, g, dim3(256), 0, st, d.plane[p], m[p], v[p], H, W, (const unsigned long long *)nullptr,
-                               (const double *)nullptr, grad ? grad[p] : (const float *)t->grads[p], t->tex[p], a);
-        HIP_TRY(hipGetLastError());
+            NGF_LAUNCH(ii_adam_plane_kernel<false>, g, dim3(256), 0, st, d.plane[p], m[p], v[p], H, W, (const unsigned long long *)nullptr,
+                       (const double *)nullptr, grad ? grad[p] : (const float *)t->grads[p], t->tex[p], a);
     }
-    AdamDense<kIiDense> D;
-    int32_t at = 0;
-    for (int j = 0; j < kIiDense; ++j) {
-        const int k = 3 + j;
-        D.p[j] = (float *)ps[k]; D.m[j] = m[k]; D.v[j] = v[k]; D.g[j] = grad ? grad[k] : (const float *)t->grads[k];
-        D.begin[j] = at;
-        D.a[j] = adam_args(step_count[k] > 0 ? step_count[k] : 1, lr[k], beta1, beta2, eps, 0.0f);
-        if (on(k)) at += (int32_t)ns[k];
-    }
-    D.begin[kIiDense] = at;
-    D.skip = nullptr;
-    if (at > 0) {
-        hipLaunchKernelGGL(adam_dense_all_kernel<kIiDense>, dim3((at + 255) / 256), dim3(256), 0, st, D);
-        HIP_TRY(hipGetLastError());
-    }
+    const float *const *g = grad;
+    if (!g) g = t->grads;
+    HIP_TRY(adam_dense_all<kIiDense>(const_cast<float *const *>(ps) + 3, m + 3, v + 3, g + 3, ns + 3, step_count + 3, lr + 3, beta1, beta2, eps,
+                                     [&](int j) { return on(3 + j); }, nullptr, st));
     return NGF_OK;
 }
 
@@ -298,29 +275,20 @@ int ngf_infoinv_train_forward(ngf_infoinv_trainer *t, const float *rays, const f
     A.rays = rays; A.jitter = jitter; A.n = n; A.S = n_samples; A.white_bg = white_bg ? 1 : 0; A.infoinv = infoinv ? 1 : 0;
     A.rgb_out = rgb_map; A.depth_out = depth_map; A.d_rgb = nullptr;
     if (!t->packed) {
-        for (int p = 0; p < 3; ++p) {
-            hipLaunchKernelGGL(ii_pack_kernel, dim3(grid_for((int64_t)(A.tex[p].H + 2) * (A.tex[p].W + 2) * kIiC)), dim3(256), 0, st,
-                               (const float *)t->desc.plane[p], A.tex[p].H, A.tex[p].W, t->tex[p]);
-            HIP_TRY(hipGetLastError());
-        }
+        for (int p = 0; p < 3; ++p)
+            NGF_LAUNCH(ii_pack_kernel, dim3(grid_for((int64_t)(A.tex[p].H + 2) * (A.tex[p].W + 2) * kIiC)), dim3(256), 0, st,
+                       (const float *)t->desc.plane[p], A.tex[p].H, A.tex[p].W, t->tex[p]);
         t->packed = true;
     }
-    hipLaunchKernelGGL(ii_prep_kernel, dim3((kIiCIn * kIiCH + 255) / 256), dim3(256), 0, st, A, t->dw1t, t->cw1t);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(ii_prep_kernel, dim3((kIiCIn * kIiCH + 255) / 256), dim3(256), 0, st, A, t->dw1t, t->cw1t);
     const int64_t pairs = n * (int64_t)n_samples;
-    hipLaunchKernelGGL(ii_density_fwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(ii_density_fwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);
     const unsigned rg = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ii_scan_kernel, dim3(rg), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_prefix_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)A.count, n, A.offset);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_list_kernel, dim3(rg), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_color_fwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);       // the active count is read on the device
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ii_composite_fwd_kernel, dim3(rg), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(ii_scan_kernel, dim3(rg), dim3(256), 0, st, A);
+    NGF_LAUNCH(ii_prefix_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)A.count, n, A.offset);
+    NGF_LAUNCH(ii_list_kernel, dim3(rg), dim3(256), 0, st, A);
+    NGF_LAUNCH(ii_color_fwd_kernel, dim3(grid_for(pairs)), dim3(256), 0, st, A);       // the active count is read on the device
+    NGF_LAUNCH(ii_composite_fwd_kernel, dim3(rg), dim3(256), 0, st, A);
     static int64_t next_ticket = 0;
     t->ticket = __atomic_add_fetch(&next_ticket, 1, __ATOMIC_RELAXED);
     *ticket = t->ticket;
@@ -339,11 +307,9 @@ int ngf_infoinv_train_backward_grad(ngf_infoinv_trainer *t, int64_t ticket, cons
     int rc;
     if ((rc = ii_backward_deltas(t, st))) return rc;
     const int64_t n = A.n, pairs = n * (int64_t)A.S;
-    for (int p = 0; p < 3; ++p) {
-        hipLaunchKernelGGL(ii_plane_grad_kernel, dim3(grid_for((int64_t)kIiC * A.tex[p].H * A.tex[p].W)), dim3(256), 0, st,
-                           (const unsigned long long *)t->gacc[p], (const double *)A.bound, A.tex[p].H, A.tex[p].W, t->grads[p]);
-        HIP_TRY(hipGetLastError());
-    }
+    for (int p = 0; p < 3; ++p)
+        NGF_LAUNCH(ii_plane_grad_kernel, dim3(grid_for((int64_t)kIiC * A.tex[p].H * A.tex[p].W)), dim3(256), 0, st,
+                   (const unsigned long long *)t->gacc[p], (const double *)A.bound, A.tex[p].H, A.tex[p].W, t->grads[p]);
     // weight gradients (which: 3..8 density mlp.{0,2,4}.{weight,bias}, 9 basis, 10..15 rgb mlp.{0,2,4}.{weight,bias})
     const int32_t *na = A.offset + n;
     const IiProductBufs B = ii_bufs(t);
@@ -354,9 +320,7 @@ int ngf_infoinv_train_backward_grad(ngf_infoinv_trainer *t, int64_t ticket, cons
         (rc = ii_xty(B, A.c_d2, A.c_h1, pairs, na, kIiCH, kIiCH, t->grads[12], t->grads[13], nullptr, st)) ||
         (rc = ii_xty(B, A.c_d3, A.c_h2, pairs, na, 3, kIiCH, t->grads[14], t->grads[15], nullptr, st)))
         return rc;
-    hipLaunchKernelGGL(ii_unfold_kernel, dim3((kIiCF * kIiCF + 255) / 256), dim3(256), 0, st, (const double *)t->m64, A.basis, A.w1, t->grads[10],
-                       t->grads[9]);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(ii_unfold_kernel, dim3((kIiCF * kIiCF + 255) / 256), dim3(256), 0, st, (const double *)t->m64, A.basis, A.w1, t->grads[10], t->grads[9]);
     t->have_grads = true;
     return NGF_OK;
 }
@@ -402,21 +366,18 @@ int ngf_infoinv_train_step_backward(ngf_infoinv_trainer *t, const float *rays, c
         if ((rc = ngf_infoinv_train_forward(t, rays + a * 6, jitter ? jitter + a : nullptr, nc, n_samples, white_bg, infoinv, t->f_rgb, t->f_depth, &ticket,
                                             hip_stream)))
             return rc;
-        hipLaunchKernelGGL(ii_loss_kernel, dim3(1), dim3(1024), 0, st, (const float *)t->f_rgb, rgb_train + a * 3, nc * 3, n * 3, t->f_drgb, loss_out,
-                           acc ? 1 : 0);
-        HIP_TRY(hipGetLastError());
+        NGF_LAUNCH(ii_loss_kernel, dim3(1), dim3(1024), 0, st, (const float *)t->f_rgb, rgb_train + a * 3, nc * 3, n * 3, t->f_drgb, loss_out, acc ? 1 : 0);
         A.d_rgb = t->f_drgb;
         if ((rc = ii_backward_deltas(t, st))) return rc;
         if (!one)
             for (int p = 0; p < 3; ++p) {
                 const unsigned g = grid_for((int64_t)kIiC * A.tex[p].H * A.tex[p].W);
                 if (acc)
-                    hipLaunchKernelGGL(ii_plane_grad_add_kernel, dim3(g), dim3(256), 0, st, (const unsigned long long *)t->gacc[p], (const double *)A.bound,
-                                       A.tex[p].H, A.tex[p].W, t->grads[p]);
+                    NGF_LAUNCH(ii_plane_grad_add_kernel, dim3(g), dim3(256), 0, st, (const unsigned long long *)t->gacc[p], (const double *)A.bound,
+                               A.tex[p].H, A.tex[p].W, t->grads[p]);
                 else
-                    hipLaunchKernelGGL(ii_plane_grad_kernel, dim3(g), dim3(256), 0, st, (const unsigned long long *)t->gacc[p], (const double *)A.bound,
-                                       A.tex[p].H, A.tex[p].W, t->grads[p]);
-                HIP_TRY(hipGetLastError());
+                    NGF_LAUNCH(ii_plane_grad_kernel, dim3(g), dim3(256), 0, st, (const unsigned long long *)t->gacc[p], (const double *)A.bound,
+                               A.tex[p].H, A.tex[p].W, t->grads[p]);
             }
         const int64_t pairs = nc * (int64_t)n_samples;
         const int32_t *na = A.offset + nc;
@@ -429,10 +390,8 @@ int ngf_infoinv_train_step_backward(ngf_infoinv_trainer *t, const float *rays, c
             (rc = ii_mm(B, A.c_d3, A.c_h2, pairs, na, 3, kIiCH, t->grads[14], t->grads[15], nullptr, acc, st)))
             return rc;
     }
-    hipLaunchKernelGGL(ii_unfold_kernel, dim3((kIiCF * kIiCF + 255) / 256), dim3(256), 0, st, (const double *)t->m64, A.basis, A.w1, t->grads[10],
-                       t->grads[9]);
-    HIP_TRY(hipGetLastError());
-    t->ticket = 0;                   // the trainer's own d rgb_map went through: no autograd backward belongs to these forwards
+    NGF_LAUNCH(ii_unfold_kernel, dim3((kIiCF * kIiCF + 255) / 256), dim3(256), 0, st, (const double *)t->m64, A.basis, A.w1, t->grads[10], t->grads[9]);
+    t->ticket = 0;                  // the trainer's own d rgb_map went through: no autograd backward belongs to these forwards
     t->have_grads = false;
     t->have_fused = true;
     t->planes_fixed = one;
@@ -447,9 +406,8 @@ int ngf_infoinv_train_get_grad(ngf_infoinv_trainer *t, int32_t which, float *out
     DeviceScope ds(t->device);
     if (which < 3 && t->planes_fixed) {
         const Tex &x = t->A.tex[which];
-        hipLaunchKernelGGL(ii_plane_grad_kernel, dim3(grid_for((int64_t)kIiC * x.H * x.W)), dim3(256), 0, st, (const unsigned long long *)t->gacc[which],
-                           (const double *)t->A.bound, x.H, x.W, out);
-        HIP_TRY(hipGetLastError());
+        NGF_LAUNCH(ii_plane_grad_kernel, dim3(grid_for((int64_t)kIiC * x.H * x.W)), dim3(256), 0, st, (const unsigned long long *)t->gacc[which],
+                   (const double *)t->A.bound, x.H, x.W, out);
         return NGF_OK;
     }
     HIP_TRY(hipMemcpyAsync(out, t->grads[which], (size_t)t->grad_elems[which] * sizeof(float), hipMemcpyDeviceToDevice, st));

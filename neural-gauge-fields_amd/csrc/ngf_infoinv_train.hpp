@@ -262,23 +262,9 @@ __global__ void __launch_bounds__(256) ii_scan_kernel(const IiArgs A)
 
 __global__ void __launch_bounds__(1024) ii_prefix_kernel(const int32_t *count, int64_t n, int32_t *offset)
 {
-    __shared__ int32_t part[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024;
-    const int64_t lo = t * per, hi = lo + per < n ? lo + per : n;
-    int32_t s = 0;
-    for (int64_t k = lo; k < hi; ++k) s += count[k];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int32_t v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int32_t run = part[t] - s;
-    for (int64_t k = lo; k < hi; ++k) { offset[k] = run; run += count[k]; }
-    if (t == 1023) offset[n] = part[1023];
+    __shared__ int32_t sh[1024];
+    const int32_t total = block_scan_runs(count, n, offset, sh);
+    if (threadIdx.x == 1023) offset[n] = total;
 }
 
 __global__ void __launch_bounds__(256) ii_list_kernel(const IiArgs A)

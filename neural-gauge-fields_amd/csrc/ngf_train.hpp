@@ -10,9 +10,10 @@
 //                              (every per-sample transcendental of the step is taken here, 3.6 M samples in parallel)
 //   train_scan_kernel          sixteen lanes per ray, sequential raw2alpha (FieldBase.py:12-19) over the stored factors: weights,
 //                              active counts (pass 0) and the (ray, step)-ordered active list (pass 1): deterministic
-//   train_fold_kernel          W1' = W1[:, :144] . basis and the padded / transposed LDS images of the colour MLP
-//   train_color_fwd_kernel     16 active samples per wave pass on v_mfma_f32_16x16x4_f32: [144 colour features, view] -> 64 ->
-//                              64 -> 3 sigmoid; colours to the dense buffer, activations to HBM rows
+//   train_fold_kernel          W1' = W1[:, :144] . basis and the two LDS images of the colour MLP: the forward's in the eval pass's layout
+//                              (MlpLayout16<48>), the backward's padded and transposed
+//   train_color_fwd16_kernel   16 active samples per wave pass in the eval pass's shape (ngf_shade16.hpp, twelve waves per CU): [144 colour
+//                              features, view] -> 64 -> 64 -> 3 sigmoid; colours to the dense buffer, activation rows to HBM from registers
 //   train_composite_bwd_kernel sixteen lanes per ray: rgb_map, clamp, residual, loss; then d loss / d xs for every sample from
 //                              the closed form of the cumprod backward (two sequential sweeps, no gathers)
 //   train_color_bwd_kernel     the data gradients of the colour MLP with the TRANSPOSED weights on the matrix pipe, d loss / d t, the
@@ -24,16 +25,16 @@
 //   train_density_bwd_kernel   every valid sample: ONE scalar per tap into the density-gradient images (the decoder is linear:
 //                              rank-one gradient, expanded by train_density_finish_kernel), d loss / d t -> gauge planes
 //   adam_*_kernel              torch.optim.Adam's update; planes read their gradient from the packed layout and add the L1 term
-// ngf_train_backward (ngf_field.hip) runs the weight-gradient GEMMs, the colour-plane scatter and the density backward side by side on
+// ngf_train_backward (ngf_train.hip) runs the weight-gradient GEMMs, the colour-plane scatter and the density backward side by side on
 // three streams after the colour backward (event fork / join; the caller's stream order is kept).
 //
 // basis has neither bias nor activation (networks.py:17,26), so layer 1 acts on the features through W1' = W1[:, :144] . basis
 // (64 x 144).  train_fold_kernel rebuilds W1' from the current weights every step (float64 accumulate); forward and data
 // gradients then need ONE 160-wide layer instead of a 144x144 product plus a 160-wide layer, and by the chain rule
 //     M = Delta1^T F (64 x 144, the only big sample reduction)   ->   dW1[:, :144] = M . basis^T ,  d basis = W1[:, :144]^T . M
-// so g = basis . f is never materialised.  W1', W2 (and their transposes for the backward) are padded to bank-conflict-free
-// strides and live in LDS for the whole kernel (57-61 KB per workgroup); tiles of 16 samples live in wave-private LDS as
-// [k][16] so that a lane's MFMA B operand is in[k][sample].
+// so g = basis . f is never materialised.  The backward's W1'^T and W2^T are padded to a bank-conflict-free stride and live in LDS
+// for the whole kernel (57 KB per workgroup); its tiles of 16 samples live in wave-private LDS as [k][16] so that a lane's MFMA B
+// operand is in[k][sample].
 #pragma once
 #include "ngf_adam.hpp"
 #include "ngf_device.hpp"
@@ -42,20 +43,16 @@
 
 namespace ngf {
 
-constexpr int kTrainWaves = 6;                 // waves per workgroup in the colour forward kernel (H2 overwrites the dead feature tile)
 #ifndef NGF_TRAIN_WAVES_BWD
 #define NGF_TRAIN_WAVES_BWD 7
 #endif
-constexpr int kTrainWavesBwd = NGF_TRAIN_WAVES_BWD;              // ... and in the colour backward kernel (its tiles alias, see kBwdTileFloats)
+constexpr int kTrainWavesBwd = NGF_TRAIN_WAVES_BWD;              // waves per workgroup in the colour backward kernel (its tiles alias, see kBwdTileFloats)
 constexpr int kFeat = 144;                     // colour features (3 planes x 48)
 constexpr int kIn1 = 159, kIn1Pad = 160;       // [g(144), view(15)] (+1 zero pad)
 constexpr int kTs = 17;                        // row stride of the wave tiles [k][kTs]: odd, so that BOTH the MFMA operand reads (16 samples of a row) and the
                                                // row <-> global-row transposes (64 rows of one sample) spread over the banks (stride 16: 32 lanes per bank)
-constexpr int kLd1 = 164, kLd2 = 68;           // LDS row strides == 4 (mod 32): lane (row n, k = 4j+q) -> bank 4n+q, two lanes per bank
-// forward image : W1' [64][kLd1] (cols 144..158 = W1's view columns, 159 = 0) | W2 [64][kLd2] | W3 [3][64] | b1 [64] | b2 [64] | b3 [4]
+constexpr int kLd2 = 68;                       // LDS row stride == 4 (mod 32): lane (row n, k = 4j+q) -> bank 4n+q, two lanes per bank
 // backward image: W1'^T [144][kLd2] | W2^T [64][kLd2] | W3 [3][64]
-constexpr int kFwdW1 = 0, kFwdW2 = kFwdW1 + 64 * kLd1, kFwdW3 = kFwdW2 + 64 * kLd2, kFwdB1 = kFwdW3 + 192, kFwdB2 = kFwdB1 + 64, kFwdB3 = kFwdB2 + 64,
-              kFwdImage = kFwdB3 + 4;
 constexpr int kBwdW1T = 0, kBwdW2T = kBwdW1T + kFeat * kLd2, kBwdW3 = kBwdW2T + 64 * kLd2, kBwdImage = kBwdW3 + 192;
 
 struct TrainArgs {
@@ -80,8 +77,8 @@ struct TrainArgs {
     float *list_w;           // [cap]
     // activations of the current chunk, sample-major rows
     float *F, *V, *H1, *H2, *D3, *D2, *D1;          // [chunk, 144|16|64|64|16|64|64]  (V = the 15 view inputs + 0)
-    const float *fwd_image, *bwd_image;             // LDS images built by train_fold_kernel
-    const float *fwd16_image;                       // the forward's image in the eval pass's layout (MlpLayout16<48>, ngf_shade16.hpp), train_color_fwd16_kernel
+    const float *bwd_image;                         // LDS images built by train_fold_kernel: the backward's (train_color_bwd_kernel) ...
+    const float *fwd16_image;                       // ... and the forward's, in the eval pass's layout (MlpLayout16<48>, ngf_shade16.hpp), train_color_fwd16_kernel
     float *M;                                       // [64,144] = Delta1^T F, accumulated over the chunks
     // colour-plane scatter by bins (section 5b): a bin = the cells of one 8x8 block of one colour plane
     float *DF;                                      // [chunk, 144]  d loss / d colour features of the chunk's samples
@@ -324,36 +321,18 @@ __global__ void __launch_bounds__(64) train_scan_kernel(const TrainArgs T, int p
     if (live && seg == 0) T.count[r] = cnt;
 }
 
-// exclusive prefix of count[0..n) -> offset[0..n]; one block: every thread sums a run of consecutive counts, ONE scan over the 1024 run
-// sums, then the run is written (round 2 scanned chunk after chunk of 1024: 80 barriers for a 4096-ray batch, 10 us)
+// exclusive prefix of count[0..n) -> offset[0..n]; one block (block_scan_runs, ngf_device.hpp)
 // rows_cap / overflow (speculative rows, ngf_train_desc::chunk_samples < 0): when the batch has more active samples than the trainer keeps
 // activation rows for, overflow[0] = 1 for THIS step (the Adam kernels then leave parameters and moments alone: a truncated gradient is never
 // applied) and the sticky counter overflow[1] goes up (ngf_train_overflow_count); otherwise overflow[0] = 0.
 __global__ void __launch_bounds__(1024) train_prefix_kernel(const int32_t *count, int64_t n, int32_t *offset, int64_t rows_cap = 0, int32_t *overflow = nullptr)
 {
-    __shared__ int sh[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024;
-    const int64_t b0 = t * per, b1 = b0 + per < n ? b0 + per : n;
-    int c = 0;
-    for (int64_t b = b0; b < b1; ++b) c += count[b];
-    sh[t] = c;
-    __syncthreads();
-    for (int s = 1; s < 1024; s <<= 1) {
-        const int add = t >= s ? sh[t - s] : 0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    int run = sh[t] - c;
-    for (int64_t b = b0; b < b1; ++b) {
-        offset[b] = run;
-        run += count[b];
-    }
-    if (t == 1023) {
-        offset[n] = sh[1023];
+    __shared__ int32_t sh[1024];
+    const int32_t total = block_scan_runs(count, n, offset, sh);
+    if (threadIdx.x == 1023) {
+        offset[n] = total;
         if (overflow) {
-            const int over = rows_cap > 0 && (int64_t)sh[1023] > rows_cap;
+            const int over = rows_cap > 0 && (int64_t)total > rows_cap;
             overflow[0] = over;
             if (over) overflow[1] += 1;
         }
@@ -459,17 +438,16 @@ __device__ __forceinline__ void list_sample_coords(const RenderArgs &A, int64_t 
     triplane_gauge(A, xn, A.mode, t);
 }
 
-constexpr int kFwdTileFloats = (kIn1Pad + 64) * kTs;                       // [F; view] (H2 goes there once layer 1 is done and F is stored), H1
 constexpr int kDfStride = kFeat + 1;                                       // DF is kept sample-major (bank-conflict-free rows)
 // backward tiles per wave: [H1 | D2 | pad] is overwritten by DF^T once d1 exists and d2 / d1 have been written out; [H2, then D1]
 constexpr int kBwdTileFloats = 16 * kDfStride + 64 * kTs;
 static_assert(16 * kDfStride >= 2 * 64 * kTs, "DF^T must cover the H1 and D2 tiles it aliases");
 
 // ---- per-step weight images -------------------------------------------------------------------------------------------------
-// fwd16 (round 5): the same W1' / W2 / W3 / biases in the eval pass's image layout MlpLayout16<48> (ngf_mlp_layout.hpp: what build_field_images makes on
-// the host for a render handle) -- A operands [unit tile][k-step][lane], lane (i, kq) of k-step t = input kmap(t, kq) of unit mt * 16 + i;
-// hidden units in accumulator order n = mt * 16 + 4 kq + r.
-__global__ void __launch_bounds__(256) train_fold_kernel(const TrainArgs T, float *fwd, float *bwd, float *fwd16)
+// bwd: the backward image above.  fwd16: W1' (with W1's view columns) / W2 / W3 / biases in the eval pass's image layout MlpLayout16<48>
+// (ngf_mlp_layout.hpp: what build_field_images makes on the host for a render handle) -- A operands [unit tile][k-step][lane], lane (i, kq) of
+// k-step t = input kmap(t, kq) of unit mt * 16 + i; hidden units in accumulator order n = mt * 16 + 4 kq + r.
+__global__ void __launch_bounds__(256) train_fold_kernel(const TrainArgs T, float *bwd, float *fwd16)
 {
     using L16 = MlpLayout16<48>;
     const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
@@ -484,7 +462,6 @@ __global__ void __launch_bounds__(256) train_fold_kernel(const TrainArgs T, floa
         } else if (k < kIn1) {
             v = T.w1[m * kIn1 + k];
         }
-        fwd[kFwdW1 + m * kLd1 + k] = v;
         {   // the one (k-step, lane) of the 16-wide image that multiplies input k into unit m
             const int mt = m >> 4, iu = m & 15;
             int t16, kq;
@@ -496,7 +473,6 @@ __global__ void __launch_bounds__(256) train_fold_kernel(const TrainArgs T, floa
     for (int i = tid; i < 64 * 64; i += nth) {
         const int m = i / 64, k = i % 64;
         const float v = T.w2[m * 64 + k];
-        fwd[kFwdW2 + m * kLd2 + k] = v;
         bwd[kBwdW2T + k * kLd2 + m] = v;
         {   // input hidden unit k = mt' * 16 + 4 kq + r is k-step t = 4 mt' + r of lane quarter kq
             const int mt = m >> 4, iu = m & 15, kq = (k & 15) >> 2, t16 = 4 * (k >> 4) + (k & 3);
@@ -504,23 +480,18 @@ __global__ void __launch_bounds__(256) train_fold_kernel(const TrainArgs T, floa
         }
     }
     for (int i = tid; i < 192; i += nth) {
-        fwd[kFwdW3 + i] = T.w3[i]; bwd[kBwdW3 + i] = T.w3[i];
+        bwd[kBwdW3 + i] = T.w3[i];
         const int c = i / 64, n = i % 64, kq = (n & 15) >> 2, kk = 4 * (n >> 4) + (n & 3);         // unit n = (kk >> 2) * 16 + 4 kq + (kk & 3)
         fwd16[L16::W3 + c * 64 + kq * 16 + kk] = T.w3[i];
     }
     for (int i = tid; i < 64; i += nth) {
-        fwd[kFwdB1 + i] = T.b1[i]; fwd[kFwdB2 + i] = T.b2[i];
         const int kq = (i & 15) >> 2, kk = 4 * (i >> 4) + (i & 3);
         fwd16[L16::B1 + kq * 16 + kk] = T.b1[i];
         fwd16[L16::B2 + kq * 16 + kk] = T.b2[i];
     }
-    for (int i = tid; i < 4; i += nth) { fwd[kFwdB3 + i] = i < 3 ? T.b3[i] : 0.0f; fwd16[L16::B3 + i] = i < 3 ? T.b3[i] : 0.0f; }
+    for (int i = tid; i < 4; i += nth) fwd16[L16::B3 + i] = i < 3 ? T.b3[i] : 0.0f;
     // pad columns (never multiplied by a non-zero operand, but keep them defined)
-    for (int i = tid; i < 64 * (kLd1 - kIn1Pad); i += nth) fwd[kFwdW1 + (i / (kLd1 - kIn1Pad)) * kLd1 + kIn1Pad + i % (kLd1 - kIn1Pad)] = 0.0f;
-    for (int i = tid; i < 64 * (kLd2 - 64); i += nth) {
-        fwd[kFwdW2 + (i / (kLd2 - 64)) * kLd2 + 64 + i % (kLd2 - 64)] = 0.0f;
-        bwd[kBwdW2T + (i / (kLd2 - 64)) * kLd2 + 64 + i % (kLd2 - 64)] = 0.0f;
-    }
+    for (int i = tid; i < 64 * (kLd2 - 64); i += nth) bwd[kBwdW2T + (i / (kLd2 - 64)) * kLd2 + 64 + i % (kLd2 - 64)] = 0.0f;
     for (int i = tid; i < kFeat * (kLd2 - 64); i += nth) bwd[kBwdW1T + (i / (kLd2 - 64)) * kLd2 + 64 + i % (kLd2 - 64)] = 0.0f;
 }
 
@@ -542,124 +513,16 @@ __global__ void __launch_bounds__(256) train_unfold_kernel(const TrainArgs T, fl
     }
 }
 
-// ---- 3. colour forward over the active list -------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kTrainWaves * 64) __attribute__((amdgpu_waves_per_eu(1, 2))) train_color_fwd_kernel(const TrainArgs T)
-{
-    NGF_KARG_CONTRACT_T(&train_color_fwd_kernel, TrainArgs);      // TrainArgs starts with its RenderArgs (static_assert above)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const RenderArgs &A = T.R;
-    for (int i = threadIdx.x; i < kFwdImage; i += blockDim.x) smem[i] = T.fwd_image[i];
-    __syncthreads();
-    const float *img = smem;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = lane & 15, q = lane >> 4;
-    float *Ft = smem + ((kFwdImage + 3) & ~3) + wave * kFwdTileFloats, *H1t = Ft + kIn1Pad * kTs, *H2t = Ft;
-    const int chunk_n = chunk_rows(T);
-    const int passes = (chunk_n + 15) / 16;
-    // The list entries of a pass and what hangs on them -- ray, gauge-shifted coordinates: three dependent global reads before the first
-    // feature tap can be requested -- are fetched during the wave's PREVIOUS pass (requests unconditional: past the last pass, that pass again).
-    const int stride = gridDim.x * kTrainWaves;
-    auto want_list = [&](int ps, int &r_, int &i_) {
-        const int lc = ps * 16 + n;
-        const int64_t sl = T.chunk_base + (lc < chunk_n ? lc : 0);
-        r_ = T.list[2 * sl]; i_ = T.list[2 * sl + 1];
-    };
-    auto want_coords = [&](int r_, int i_, float (&t_)[6], float (&d_)[3]) {
-        float xn_[3];
-        list_sample_coords(A, r_, i_, t_, xn_);
-        d_[0] = A.rays[(int64_t)r_ * 6 + 3]; d_[1] = A.rays[(int64_t)r_ * 6 + 4]; d_[2] = A.rays[(int64_t)r_ * 6 + 5];
-    };
-    int pass = blockIdx.x * kTrainWaves + wave;
-    int r_cur = 0, i_cur = 0;
-    float t[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, dcur[3] = {0.0f, 0.0f, 1.0f};
-    if (pass < passes) {
-        want_list(pass, r_cur, i_cur);
-        want_coords(r_cur, i_cur, t, dcur);
-    }
-    for (; pass < passes; pass += stride) {
-        const int local = pass * 16 + n;
-        const bool live = local < chunk_n;
-        const int64_t r = r_cur;
-        const int i = i_cur;
-        const int next = pass + stride < passes ? pass + stride : pass;
-        int r_nx, i_nx;
-        want_list(next, r_nx, i_nx);
-        // compute_rgb's fetch (Field.py:93-103): lane (q, n) interpolates channels 12q .. 12q+11 of every plane for sample n
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const Tex &tx = A.app[p];
-            Bil b = bil_setup(t[2 * p], t[2 * p + 1], tx);
-            const f32x4 *q00 = reinterpret_cast<const f32x4 *>(tx.p + (size_t)b.idx * 48) + 3 * q;
-            const f32x4 *q01 = q00 + (size_t)tx.stride * 12;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                f32x4 v00 = q00[j], v10 = q00[12 + j], v01 = q01[j], v11 = q01[12 + j];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) Ft[(p * 48 + 12 * q + 4 * j + e) * kTs + n] = live ? bil_mix(b, v00[e], v10[e], v01[e], v11[e]) : 0.0f;
-            }
-        }
-        // the view inputs of layer 1 (networks.py:27-29): rows 144..159 of the input tile
-        {
-            float d[3] = {dcur[0], dcur[1], dcur[2]}, v[16];
-            view_inputs(d, v);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {          // v[4q + j] by selects: a q-indexed read would put v into scratch memory
-                const float vq = q == 0 ? v[j] : (q == 1 ? v[4 + j] : (q == 2 ? v[8 + j] : v[12 + j]));
-                Ft[(kFeat + 4 * q + j) * kTs + n] = live ? vq : 0.0f;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        dense16<false, 1, 64, kIn1Pad, kIn1Pad>(img + kFwdW1, kLd1, 64, img + kFwdB1, Ft, H1t, nullptr, lane);      // relu(W1' f + W1v view + b1)
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (T.store) {          // the feature tile leaves LDS now: layer 2 writes its output over it
-            const int64_t row = live ? local : 0;
-            tile_to_rows(Ft, kFeat, T.F, kFeat, row, live, lane);
-            tile_to_rows(Ft + kFeat * kTs, 16, T.V, 16, row, live, lane);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        }
-        float t_nx[6], d_nx[3];
-        want_coords(r_nx, i_nx, t_nx, d_nx);
-        dense16<false, 1, 64, 64, 64>(img + kFwdW2, kLd2, 64, img + kFwdB2, H1t, H2t, nullptr, lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        // layer 3 + sigmoid on the VALU: lane (q, n) sums its 16 hidden units, then the four quarters meet
-        float c[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            float s = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) s = fmaf(img[kFwdW3 + j * 64 + 16 * q + k], H2t[(16 * q + k) * kTs + n], s);
-            s += __shfl_xor(s, 16);
-            s += __shfl_xor(s, 32);
-            s += img[kFwdB3 + j];
-            c[j] = 1.0f / (1.0f + expf(-s));
-        }
-        if (live && q == 0) {
-            float *dst = T.c + ((int64_t)r * A.S + i) * 3;
-            dst[0] = c[0]; dst[1] = c[1]; dst[2] = c[2];
-        }
-        if (T.store) {
-            const int64_t row = live ? local : 0;
-            tile_to_rows(H1t, 64, T.H1, 64, row, live, lane);
-            tile_to_rows(H2t, 64, T.H2, 64, row, live, lane);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        r_cur = r_nx; i_cur = i_nx;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) t[k] = t_nx[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) dcur[k] = d_nx[k];
-    }
-}
-
-// ---- 3b. colour forward in the eval pass's shape (round 5) -----------------------------------------------------------------------------------
-// train_color_fwd_kernel above keeps its tiles in LDS ([k][17] transposes between MFMA operands and sample-major rows): 152 KB per workgroup, six
-// waves per CU, 200 us for ~170 k samples -- the render kernel's level-1 shade pass does the same arithmetic for 16 samples in ~1.6 us of a SIMD
-// shared by three waves, ten times the rate.  This kernel IS that pass (gather16_issue / mix16 / layer1_plane16 of ngf_shade16.hpp, twelve waves per
-// CU, the 58.6 KB MlpLayout16<48> image train_fold_kernel now also builds) with the activation rows stored straight from the registers that hold
-// them: lane (s, kq) has channels 16 q + 4 kq .. + 3 of every plane, its four view inputs and hidden units mt * 16 + 4 kq .. + 3 of its own sample --
-// 16-byte pieces of the rows F [144], V [16], H1 [64], H2 [64] (post-ReLU, as before).  Same features to the bit (same bil_setup / bil_mix);
-// layers 1-2 sum in the MFMA's k order of the eval pass instead of dense16's: last-bit differences in H1 / H2 / colours.
+// ---- 3. colour forward over the active list, in the eval pass's shape ------------------------------------------------------------------------
+// The render kernel's level-1 shade pass does this arithmetic for 16 samples in ~1.6 us of a SIMD shared by three waves (an earlier kernel with
+// its tiles in LDS, 152 KB per workgroup and six waves per CU, ran at a tenth of that rate: DESIGN_HISTORY.md).  This kernel IS that pass
+// (gather16_issue / mix16 / layer1_plane16 of ngf_shade16.hpp, twelve waves per CU, the 58.6 KB MlpLayout16<48> image train_fold_kernel builds)
+// with the activation rows stored straight from the registers that hold them: lane (s, kq) has channels 16 q + 4 kq .. + 3 of every plane, its
+// four view inputs and hidden units mt * 16 + 4 kq .. + 3 of its own sample -- 16-byte pieces of the rows F [144], V [16], H1 [64], H2 [64]
+// (post-ReLU).  The features are bil_setup / bil_mix's bits; layers 1-2 sum in the MFMA's k order of the eval pass, not in dense16's.
 constexpr int kTrainWaves16 = 12;
+constexpr size_t kColorFwd16LdsBytes = (size_t)((MlpLayout16<48>::TOTAL + 3) & ~3) * sizeof(float);      // the launch's dynamic LDS: the image
+static_assert(kColorFwd16LdsBytes <= 160 * 1024, "colour forward LDS");
 __global__ void __launch_bounds__(kTrainWaves16 * 64) train_color_fwd16_kernel(const TrainArgs T)
 {
     NGF_KARG_CONTRACT_T(&train_color_fwd16_kernel, TrainArgs);      // gather16_issue reads the colour-plane descriptors from the kernel-argument segment
@@ -781,7 +644,7 @@ __global__ void __launch_bounds__(kTrainWaves16 * 64) train_color_fwd16_kernel(c
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) *reinterpret_cast<f32x4 *>(T.H2 + row * 64 + mt * 16 + 4 * kq) = f32x4{hr[4 * mt], hr[4 * mt + 1], hr[4 * mt + 2], hr[4 * mt + 3]};
         }
-        // layer 3 + sigmoid as train_color_fwd_kernel: the lane's 16 units, then the four quarters meet
+        // layer 3 + sigmoid on the VALU: the lane's 16 units, then the four quarters meet
         const f32x4 *w3 = reinterpret_cast<const f32x4 *>(blob + L::W3 + kq * 16);
         float c[3];
 #pragma unroll
@@ -962,6 +825,8 @@ __global__ void __launch_bounds__(64) train_composite_bwd_kernel(const TrainArgs
 }
 
 // ---- 5. colour backward over the active list --------------------------------------------------------------------------------
+constexpr size_t kColorBwdLdsBytes = (size_t)(((kBwdImage + 3) & ~3) + kTrainWavesBwd * kBwdTileFloats) * sizeof(float);      // the image + every wave's tiles
+static_assert(kColorBwdLdsBytes <= 160 * 1024, "colour backward LDS");
 __global__ void __launch_bounds__(kTrainWavesBwd * 64) __attribute__((amdgpu_waves_per_eu(1, 2))) train_color_bwd_kernel(const TrainArgs T)
 {
     NGF_KARG_CONTRACT_T(&train_color_bwd_kernel, TrainArgs);      // TrainArgs starts with its RenderArgs (static_assert above)

@@ -70,8 +70,7 @@ namespace {
 
 int launch_gemm(const UvtGemm &G, unsigned gx, unsigned gy, unsigned gz, hipStream_t st)
 {
-    hipLaunchKernelGGL(uvt_gemm_kernel, dim3(gx, gy, gz), dim3(256), 0, st, G);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(uvt_gemm_kernel, dim3(gx, gy, gz), dim3(256), 0, st, G);
     return NGF_OK;
 }
 
@@ -126,9 +125,8 @@ int bwd_weights_view(const LayerView &v, hipStream_t st)
     int rc = launch_gemm(G, blocks(v.out, 64), blocks(v.in, 64), (unsigned)std::max(1, nz), st);
     if (rc) return rc;
     const int64_t nk = (int64_t)v.out * v.in;
-    hipLaunchKernelGGL(uvt_reduce_kernel, dim3(blocks(nk)), dim3(256), 0, st, (const float *)v.part, (const float *)v.partb, nk, v.out, (int)v.rows,
-                       v.rows_dev, v.gw, v.gb);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(uvt_reduce_kernel, dim3(blocks(nk)), dim3(256), 0, st, (const float *)v.part, (const float *)v.partb, nk, v.out, (int)v.rows, v.rows_dev,
+               v.gw, v.gb);
     return NGF_OK;
 }
 
@@ -285,32 +283,25 @@ int ngf_uv_train_forward(ngf_uv_trainer *t, const float *campos, const float *ra
         UvtRays A{};
         A.cam = campos; A.raydir = raydir; A.U = jitter_u; A.ray_pos = ray_pos; A.seg = t->seg; A.cnt = t->cnt;
         A.nrays = nrays; A.R = (int32_t)rays_per_cam; A.S = S;
-        hipLaunchKernelGGL(uvt_rays_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
+        NGF_LAUNCH(uvt_rays_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
     }
-    hipLaunchKernelGGL(uvt_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)t->cnt, nrays, t->off, t->total);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(uvt_compact_kernel, dim3(blocks(nrays)), dim3(256), 0, st, (const float *)ray_pos, (const int32_t *)t->off, nrays, S, t->list, t->vid);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(uvt_pe_pos_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)ray_pos, M, t->Xga);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(uvt_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)t->cnt, nrays, t->off, t->total);
+    NGF_LAUNCH(uvt_compact_kernel, dim3(blocks(nrays)), dim3(256), 0, st, (const float *)ray_pos, (const int32_t *)t->off, nrays, S, t->list, t->vid);
+    NGF_LAUNCH(uvt_pe_pos_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)ray_pos, M, t->Xga);
     int rc = NGF_OK;
     // gauge network on every sample -> uv
     for (int l = 12; l <= 16 && !rc; ++l) rc = fwd_layer(t, l, M, nullptr, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(uvt_uv_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)t->out[16], M, t->desc.sphere, t->uv);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(uvt_uv_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)t->out[16], M, t->desc.sphere, t->uv);
     HIP_TRY(hipMemcpyAsync(uv, t->uv, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, st));
     // geometry network on the in-cube samples
-    hipLaunchKernelGGL(uvt_gather_kernel, dim3(blocks(M * 64)), dim3(256), 0, st, (const float *)t->Xga, (const int32_t *)t->list, (const int32_t *)t->total,
-                       M, t->Xg);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(uvt_gather_kernel, dim3(blocks(M * 64)), dim3(256), 0, st, (const float *)t->Xga, (const int32_t *)t->list, (const int32_t *)t->total, M,
+               t->Xg);
     for (int l = 0; l <= 11 && !rc; ++l) rc = fwd_layer(t, l, M, t->total, st);
     if (rc) return rc;
     // texture network on the in-cube samples
-    hipLaunchKernelGGL(uvt_tex_in_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)t->uv, raydir, (const int32_t *)t->list,
-                       (const int32_t *)t->total, M, D, S, t->Xt, t->X2);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(uvt_tex_in_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)t->uv, raydir, (const int32_t *)t->list, (const int32_t *)t->total,
+               M, D, S, t->Xt, t->X2);
     for (int l = 17; l <= 28 && !rc; ++l) rc = fwd_layer(t, l, M, t->total, st);
     if (rc) return rc;
     {
@@ -318,8 +309,7 @@ int ngf_uv_train_forward(ngf_uv_trainer *t, const float *campos, const float *ra
         A.seg = t->seg; A.vid = t->vid; A.raw = t->out[11]; A.c1 = t->out[23]; A.c2 = t->out[28]; A.bg = bg;
         A.color = color; A.trans = trans; A.weight = weight; A.opac = t->opac; A.acct = t->acct; A.xraw = t->xraw;
         A.nrays = nrays; A.R = (int32_t)rays_per_cam; A.S = S;
-        hipLaunchKernelGGL(uvt_composite_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
+        NGF_LAUNCH(uvt_composite_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
     }
     t->raydir = raydir; t->bg = bg; t->ray_pos = ray_pos;
     t->nrays = nrays; t->R = rays_per_cam; t->S = S;
@@ -344,8 +334,7 @@ int ngf_uv_train_backward(ngf_uv_trainer *t, int64_t ticket, const float *d_colo
         A.d_color = d_color; A.d_trans = d_trans; A.d_weight = d_weight;
         A.d_raw = t->dRaw; A.d_c1 = t->dC1; A.d_c2 = t->dC2;
         A.nrays = nrays; A.R = (int32_t)t->R; A.S = t->S;
-        hipLaunchKernelGGL(uvt_composite_bwd_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
-        HIP_TRY(hipGetLastError());
+        NGF_LAUNCH(uvt_composite_bwd_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
     }
     const int32_t *V = t->total;
     int rc = NGF_OK;
@@ -362,9 +351,8 @@ int ngf_uv_train_backward(ngf_uv_trainer *t, int64_t ticket, const float *d_colo
     if (!rc) rc = bwd_layer(t, 17, pp[cur], 256, M, V, t->dXt, 64, t->shape[17].in, nullptr, 0, kNone, st);
     if (rc) return rc;
     // d uv -> d q (every sample), gauge network
-    hipLaunchKernelGGL(uvt_uv_bwd_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)t->out[16], (const float *)t->uv, (const float *)t->dXt,
-                       (const int32_t *)t->vid, d_uv, M, t->desc.sphere, t->dQ);
-    HIP_TRY(hipGetLastError());
+    NGF_LAUNCH(uvt_uv_bwd_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)t->out[16], (const float *)t->uv, (const float *)t->dXt,
+               (const int32_t *)t->vid, d_uv, M, t->desc.sphere, t->dQ);
     rc = bwd_layer(t, 16, t->dQ, 4, M, nullptr, pp[0], 128, 128, nullptr, 0, kRelu, st);
     cur = 0;
     for (int l = 15; l >= 13 && !rc; --l, cur ^= 1)

@@ -224,21 +224,8 @@ __global__ void __launch_bounds__(256) uvt_rays_kernel(const UvtRays A)
 __global__ void __launch_bounds__(1024) uvt_scan_kernel(const int32_t *cnt, int64_t n, int32_t *off, int32_t *total)
 {
     __shared__ int32_t sh[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024, b = t * per, e = min(n, b + per);
-    int32_t s = 0;
-    for (int64_t i = b; i < e; ++i) s += cnt[i];
-    sh[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int32_t v = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        sh[t] += v;
-        __syncthreads();
-    }
-    int32_t run = sh[t] - s;
-    for (int64_t i = b; i < e; ++i) { off[i] = run; run += cnt[i]; }
-    if (t == 1023) *total = sh[1023];
+    const int32_t sum = block_scan_runs(cnt, n, off, sh);
+    if (threadIdx.x == 1023) *total = sum;
 }
 
 // list[v] = flat sample index of in-cube sample v (ray-major, sample order); vid[m] = v or -1

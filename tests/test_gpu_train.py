@@ -462,6 +462,42 @@ def test_single_parameter_adam_entry_point():
         assert rel(a, b) < GRAD_TOL, (name, rel(a, b))
 
 
+def test_refused_adam_all_has_changed_nothing():
+    """ngf_train_adam_all checks everything ngf_train_adam would refuse BEFORE it forks or launches.  After ngf_train_params_changed every packed
+    copy is stale; ngf_train_adam_ext on plane 1 alone (the caller's own moments) makes that one copy fresh again.  ngf_train_adam_all over all
+    fifteen parameters must then return NGF_E_ARG (planes 0 and 2 and the gauge planes are stale) with no parameter and no moment of the trainer
+    touched -- not with plane 1 updated on a side stream that nobody joined."""
+    import ctypes as C
+    from ngf_amd import _lib
+    NGF_E_ARG = 1
+    g, params = load_train_case("train_r1")
+    f = field_for_case(g, params, None)
+    S = int(g["S"])
+    rays, tgt, jit = torch.from_numpy(g["rays"]).cuda(), torch.from_numpy(g["rgb_train"]).cuda(), torch.from_numpy(g["jitter0"])
+    tr = train.Trainer(f, batch_size=rays.shape[0], max_samples=S)
+    tr.backward(rays, tgt, S, white_bg=True, iteration=0, jitter=jit)
+    L = _lib.lib()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    n = len(train.PARAM_NAMES)
+    _lib.check(L.ngf_train_params_changed(tr._h))
+    grad1 = tr.gradient(1).contiguous()
+    m1, v1 = torch.zeros_like(tr.params[1]), torch.zeros_like(tr.params[1])
+    grads, ms, vs, counts = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int32 * n)()
+    grads[1], ms[1], vs[1], counts[1] = grad1.data_ptr(), m1.data_ptr(), v1.data_ptr(), 1
+    lrs = (C.c_float * n)(*[float(x) for x in tr.lr])
+    _lib.check(L.ngf_train_adam_ext(tr._h, grads, ms, vs, counts, lrs, 0.9, 0.99, 1e-8, st))
+    torch.cuda.synchronize()
+    tensors = list(tr.params) + list(tr.exp_avg) + list(tr.exp_avg_sq)
+    assert len(tensors) == 45
+    snaps = [x.detach().clone() for x in tensors]
+    rc = L.ngf_train_adam_all(tr._h, (C.c_int32 * n)(*([1] * n)), lrs, 0.9, 0.99, 1e-8, 8e-5, st)
+    torch.cuda.synchronize()
+    assert rc == NGF_E_ARG, (rc, L.ngf_last_error())
+    names = [kind + name for kind in ("", "exp_avg.", "exp_avg_sq.") for name in train.PARAM_NAMES]
+    for name, x, s in zip(names, tensors, snaps):
+        assert torch.equal(x.detach().view(torch.int32), s.view(torch.int32)), name          # bit for bit
+
+
 def test_forked_and_one_stream_steps_agree_and_keep_the_callers_stream_order():
     """ngf_train_backward / ngf_train_adam_all run three chains of kernels on the trainer's own streams (event fork / join).  The same three
     iterations on ONE stream (ngf_debug_set("ablate", 1 << 19)) must give the same gradients and parameters up to the order of the float
