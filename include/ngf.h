@@ -467,6 +467,33 @@ int ngf_uv_texture_edit(const ngf_uv *m, const float *uv, const float *orig, int
 enum { NGF_UV_TEX_DIFFUSE = 1 };
 int ngf_uv_texture_eval(const ngf_uv *m, const float *uv, const float *view, int32_t view_stride, int64_t n, int32_t flags, float *out,
                         void *hip_stream);
+/* Point queries: the three networks of the handle at n explicit WORLD points xyz [n,3] (device floats) -- what the reference's
+ * net_geometry_decoder(pts)["density"] (decoder.py:219-237), gauge_transform(pts) (gauge_fields.py:60-74) and net_texture(uv, view)
+ * (decoder.py:56-121) give.  The non-NULL outputs select the parts; a part that is not asked for does not run:
+ *   sigma [n]    softplus of the geometry network (671 744 MAC per point).  CLIP (default): sigma is exactly 0.0f where not all |xyz_k| < 1, the
+ *                render's strict in-cube test (renderer.py:137-139) -- the density the renderer sees; NGF_UV_QUERY_NO_CLIP gives the network's
+ *                value everywhere.
+ *   uv [n,3]     the gauge: normalize(q) (sphere) or (tanh(q_0), tanh(q_1), 0) (square); 45 376 | 45 248 MAC per point.  Never clipped.
+ *   rgb [n,3]    the texture network at the point's own uv (the gauge runs for it whether uv is stored or not) and view: ONE direction float[3]
+ *                (view_stride 0) or one per point [n,3] (view_stride 3), used as given; with NGF_UV_TEX_DIFFUSE the viewdir=None colour of
+ *                ngf_uv_texture_eval (view ignored).  With an edit texture set the colour goes through the edit stage.  Never clipped.
+ * The formulation is always fp32 on the matrix pipe, the render's default kernel layer for layer; a handle created with NGF_UV_F_SPLIT_BF16 is
+ * served by the SAME fp32 path.  A point's value of an output is the same bits whichever other outputs are requested, whatever n and the
+ * point's place in the list, and rgb is bit for bit ngf_uv_texture_eval at the uv returned.  No atomics; the handle's state is not touched.
+ * The positional encodings are exact to 1.6 ulp of 1 for |xyz_k| <= 4 (arguments up to 2048); further out they degrade, finite.
+ * ngf_uv_density_lattice: sigma [nx,ny,nz] (C order: linear index (i ny + j) nz + k) at the points
+ *   (lo_x + float(i) * step_x, lo_y + float(j) * step_y, lo_z + float(k) * step_z), each a float32 multiply rounded, then a float32 add
+ *   rounded (no fused multiply-add): a float32 restatement has the same points bit for bit, and the values are those of ngf_uv_query on them.
+ *   No point list exists anywhere.  volume[i,j,k] is the density at (x_i, y_j, z_k): the axis convention of ngf_mesh_count / ngf_mesh_emit.
+ *   With the clip, a lattice that reaches the cube's faces is 0 on its boundary and an iso-surface of a positive level closes.
+ * Both are asynchronous on the stream; n == 0 returns NGF_OK.  NGF_E_ARG, before any GPU work: null m / xyz / lo / step / lattice sigma, no output
+ * requested, rgb without view unless diffuse, view_stride outside {0, 3}, unknown flag bits, n < 0, a lattice axis below 2 (or above 2^24),
+ * a non-finite lo or step. */
+enum { NGF_UV_QUERY_NO_CLIP = 2 };  /* shares the flag word with NGF_UV_TEX_DIFFUSE */
+int ngf_uv_query(const ngf_uv *m, const float *xyz, int64_t n, const float *view, int32_t view_stride, int32_t flags,
+                 float *sigma /*[n] or NULL*/, float *uv /*[n,3] or NULL; z = 0 for square*/, float *rgb /*[n,3] or NULL*/, void *hip_stream);
+int ngf_uv_density_lattice(const ngf_uv *m, const float lo[3], const float step[3], int32_t nx, int32_t ny, int32_t nz, int32_t flags,
+                           float *sigma /*[nx,ny,nz]*/, void *hip_stream);
 /* Replaces NeuTex.forward's colour outputs for one camera (model.py:30-52):
  *   campos_host float[3], bg_host float[3] or NULL (HOST pointers), raydir [R,3], jitter_u [R,S] = the uniforms
  *   cube_ray_generation draws with torch.rand (renderer.py:112-117; jitter = 0.05 always, model.py:30);

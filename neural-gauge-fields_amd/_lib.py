@@ -33,7 +33,7 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_uv_train_backward", "ngf_uv_train_get_grads", "ngf_uv_train_params_changed", "ngf_uv_texture_eval", "ngf_debug_uvt_gemm",
            "ngf_debug_ii_product", "ngf_debug_ii_counts",
            "ngf_mesh_workspace_bytes", "ngf_mesh_count", "ngf_mesh_emit", "ngf_debug_mesh_scan",
-           "ngf_field_query"]
+           "ngf_field_query", "ngf_uv_query", "ngf_uv_density_lattice"]
 
 
 class FieldDesc(C.Structure):
@@ -60,7 +60,8 @@ class UvDesc(C.Structure):
 
 
 UV_F_SPLIT_BF16 = 1
-UV_TEX_DIFFUSE = 1          # ngf_uv_texture_eval flags
+UV_TEX_DIFFUSE = 1          # ngf_uv_texture_eval / ngf_uv_query flags
+UV_QUERY_NO_CLIP = 2        # ngf_uv_query / ngf_uv_density_lattice flags
 MESH_FLIP, MESH_NORMALS = 1, 2      # ngf_mesh_emit flags
 QUERY_NO_MASK = 1                   # ngf_field_query flags
 
@@ -118,7 +119,10 @@ def _load(path):
         L.ngf_uv_set_texture.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.ngf_uv_texture_edit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ngf_uv_texture_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
-        L.ngf_pack_mask_bits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.ngf_uv_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ngf_uv_density_lattice.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p]
+        L.ngf_pack_mask_bits.argtypes =[C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ngf_resize_bilinear.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         L.ngf_eval_workspace_bytes.restype = C.c_int64
         L.ngf_eval_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

@@ -1,5 +1,6 @@
 """Mesh export on the GPU: marching cubes over a dense float volume (csrc/ngf_mesh.hip), the reference's
-``convert_sdf_samples_to_ply`` (TriPlane/utils.py:179-239) on top of it, and a binary PLY writer in numpy (there is no ``plyfile``).
+``convert_sdf_samples_to_ply`` (TriPlane/utils.py:179-239) on top of it, and a binary PLY writer in numpy (there is no ``plyfile``).  For NeuTex
+(uvmapping.NeuTex.export_mesh): ``atlas_coords`` (gauge uv -> OBJ texture coordinates in the exported atlas), ``unwrap_seam`` and ``write_obj``.
 
 The triangulation is the table of ``ngf_amd.mesh_table``: the usual one-vertex-per-crossing-edge definition, closed and consistently
 oriented, but NOT skimage's Lewiner tables -- vertex and face ORDER (and the split of a cell's polygons into triangles) differ from
@@ -92,6 +93,108 @@ def write_ply(path, verts, faces, normals=None, colors=None):
         fh.write(header.encode('ascii'))
         fh.write(vrec.tobytes())
         fh.write(rec.tobytes())
+
+
+def atlas_coords(uv, primitive_type, resolution=None):
+    """OBJ texture coordinates ``[..., 2]`` = (s left to right, t bottom to top) of gauge outputs ``uv`` [..., 2|3] in the atlas image the
+    NeuTex exporters write -- defined by those images: a point the exporter evaluates maps to the centre of the texel that holds its colour.
+
+    square  (``_export_square(R)`` [R,R,3], row i <-> uv_0, column j <-> uv_1):  s = (uv_1 + 1) / 2,  t = 1 - (uv_0 + 1) / 2
+    sphere  (``_export_sphere(R)`` [R,2R,3], equirectangular, rows flipped; the image depends on R through its half-texel offset, hence
+            ``resolution``): for the unit vector (a, b, c), y = acos(-b), x = atan2(-a, -c),
+            s = ((x - pi) mod 2 pi) / (2 pi) + 0.5 / (2R),  t = y / pi + 0.5 / R
+
+    A tensor or an array, evaluated in its own dtype and (for a tensor) on its own device; s of the sphere lies in [0.5/(2R), 1 + 0.5/(2R)):
+    see ``unwrap_seam`` for the triangles that cross the image's left edge."""
+    was_tensor = torch.is_tensor(uv)
+    q = uv if was_tensor else torch.as_tensor(np.asarray(uv))
+    if not q.is_floating_point():
+        q = q.float()
+    if primitive_type == 'square':
+        if q.shape[-1] not in (2, 3):
+            raise ValueError(f"atlas_coords: square uv must be [..., 2] (or [..., 3], z ignored), got {tuple(q.shape)}")
+        st = torch.stack([(q[..., 1] + 1) / 2, 1 - (q[..., 0] + 1) / 2], dim=-1)
+    elif primitive_type == 'sphere':
+        if q.shape[-1] != 3:
+            raise ValueError(f"atlas_coords: sphere uv must be [..., 3], got {tuple(q.shape)}")
+        if resolution is None or int(resolution) < 1:
+            raise ValueError("atlas_coords: the sphere atlas needs the resolution R of its [R,2R] image")
+        R = int(resolution)
+        y = torch.acos((-q[..., 1]).clamp(-1, 1))
+        x = torch.atan2(-q[..., 0], -q[..., 2])
+        s = torch.remainder(x - np.pi, 2 * np.pi) / (2 * np.pi) + 0.5 / (2 * R)
+        st = torch.stack([s, y / np.pi + 0.5 / R], dim=-1)
+    else:
+        raise ValueError(f"Unknown primitive type {primitive_type}")
+    return st if was_tensor else st.numpy()
+
+
+def unwrap_seam(faces, st):
+    """Per-corner texture indices for an atlas that is periodic in s (the sphere's): in each triangle a corner whose s lies more than 0.5 below
+    the triangle's largest s takes a duplicate of its coordinates with s + 1 (one duplicate per vertex, shared by every triangle that needs it),
+    so a triangle that fits in half a turn spans at most 0.5 in s instead of running backwards across the whole image; a renderer needs the
+    texture's repeat wrap mode (the default of the common ones) for the s > 1 corners.  (At EXACTLY half a turn the rule can leave a wider span.)  Returns ``(st_ext [nv + nd, 2], faces_vt [nt,3] int32)``
+    as numpy arrays; triangles that need nothing keep the vertices' own indices."""
+    f = (faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)).astype(np.int64).reshape(-1, 3)
+    st = st.detach().cpu().numpy() if torch.is_tensor(st) else np.asarray(st)
+    st = st.reshape(-1, 2)
+    s = st[f, 0]
+    low = s < s.max(axis=1, keepdims=True) - 0.5
+    ids, inv = np.unique(f[low], return_inverse=True)
+    dup = st[ids].copy()
+    dup[:, 0] += 1
+    faces_vt = f.copy()
+    faces_vt[low] = st.shape[0] + inv.reshape(-1)
+    return np.concatenate([st, dup], axis=0), faces_vt.astype(np.int32)
+
+
+def write_obj(path, verts, faces, st, faces_vt=None, texture=None, normals=None):
+    """Wavefront OBJ with texture coordinates: ``path`` (``v`` / ``vt`` [/ ``vn``] lines in ``%.9g``, which round-trips a float32, and
+    ``f v/vt[/vn]`` corners, 1-based), its material file (``path`` with the extension ``.mtl``) and, when ``texture`` -- a uint8 [H,W,3] array,
+    row 0 on top -- is given, the image as ``.png`` next to them, named by the material's ``map_Kd``.  ``faces_vt`` [nt,3] are the corners'
+    indices into ``st`` (default: the vertex indices); ``normals`` [nv,3] are per vertex.  An empty mesh gives a valid file with no elements."""
+    import os
+
+    def host(a, dtype):
+        return np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=dtype)
+
+    v = host(verts, np.float32).reshape(-1, 3)
+    f = host(faces, np.int64).reshape(-1, 3)
+    vt = host(st, np.float32).reshape(-1, 2)
+    fv = f if faces_vt is None else host(faces_vt, np.int64).reshape(-1, 3)
+    if fv.shape != f.shape:
+        raise ValueError(f"write_obj: faces_vt {fv.shape} does not match faces {f.shape}")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0] or fv.min() < 0 or fv.max() >= vt.shape[0]):
+        raise ValueError("write_obj: a face index points outside verts / st")
+    vn = None
+    if normals is not None:
+        vn = host(normals, np.float32).reshape(-1, 3)
+        if vn.shape != v.shape:
+            raise ValueError(f"write_obj: normals {vn.shape} do not match the {v.shape[0]} vertices")
+    stem = os.path.splitext(path)[0]
+    name = os.path.basename(stem)
+    if texture is not None:
+        from PIL import Image
+        img = np.asarray(texture)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"write_obj: texture must be uint8 [H,W,3], got {img.dtype} {img.shape}")
+        Image.fromarray(np.ascontiguousarray(img)).save(stem + ".png")
+    with open(stem + ".mtl", "w") as fh:
+        fh.write("newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\n")
+        if texture is not None:
+            fh.write(f"map_Kd {name}.png\n")
+    def rows(fmt, a, chunk=1 << 16):
+        # one formatting call per 65 536 rows (the format repeated, the block's numbers as one flat tuple): 2.5x faster than a call per row
+        return [(fmt * len(a[i:i + chunk])) % tuple(a[i:i + chunk].ravel().tolist()) for i in range(0, len(a), chunk)]
+
+    parts = [f"mtllib {name}.mtl\nusemtl atlas\n"] + rows("v %.9g %.9g %.9g\n", v) + rows("vt %.9g %.9g\n", vt)
+    if vn is not None:
+        parts += rows("vn %.9g %.9g %.9g\n", vn)
+        parts += rows("f %d/%d/%d %d/%d/%d %d/%d/%d\n", np.stack([f + 1, fv + 1, f + 1], axis=-1).reshape(-1, 9))
+    else:
+        parts += rows("f %d/%d %d/%d %d/%d\n", np.stack([f + 1, fv + 1], axis=-1).reshape(-1, 6))
+    with open(path, "w") as fh:
+        fh.write("".join(parts))
 
 
 def mesh_points(verts, bbox, offset=None, scale=None):

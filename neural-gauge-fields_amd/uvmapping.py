@@ -14,6 +14,10 @@ Texture export: ``net.net_texture.export_textures`` / ``_export_cube`` / ``_expo
 general ``NeuTex.texture_colors`` run the texture MLP on explicit points in a HIP kernel of their own (include/ngf.h: ngf_uv_texture_eval);
 ``merge_cube_to_single_texture`` (util.py:286-312) lays a cube export out as the cross image the reference's test driver saves.
 
+Point queries: ``NeuTex.query`` (density, gauge uv, colour at world points), ``NeuTex.density_lattice`` and ``NeuTex.export_mesh`` (an OBJ whose
+``vt`` coordinates map the exported atlas onto the marching-cubes surface) run the three MLPs on explicit points in a HIP kernel of their own
+(include/ngf.h: ngf_uv_query, ngf_uv_density_lattice).
+
 Training: with ``net.differentiable = True`` (an attribute, never saved) and grad enabled, ``forward`` returns the reference's training dict
 with a graph over every parameter (uv_train.py, include/ngf.h: ngf_uv_trainer_*).  Off, or under ``torch.no_grad()``, it is the eval path.
 """
@@ -221,6 +225,23 @@ class InverseGauge(nn.Module):
         return out.view(uv.shape[:-1] + (3,))
 
 
+def lattice_axes(resolution, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.0)):
+    """``(res, lo, step)`` of NeuTex.density_lattice: ``resolution`` an int or a triple (at least 2 per axis), ``step = (hi - lo) / (n - 1)`` in
+    float32.  The last point must REACH hi (at hi = 1 the clip then zeroes that slab and an iso-surface closes): where the rounded step falls
+    short -- ``lo + float32(n - 1) * step`` lands an ulp inside for 137 of the sizes up to 1024, 42 the first -- it is taken one ulp longer."""
+    res = (int(resolution),) * 3 if np.ndim(resolution) == 0 else tuple(int(r) for r in resolution)
+    if len(res) != 3 or min(res) < 2:
+        raise ValueError(f"resolution must be an int or a triple, at least 2 per axis, got {resolution!r}")
+    lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
+    last = np.asarray(res, dtype=np.float32) - np.float32(1)
+    step = (hi32 - lo32) / last
+    top = lo32 + last * step          # (float32: the product rounded, then the sum -- the kernel's arithmetic)
+    short = np.where(step > 0, top < hi32, top > hi32)
+    step = np.where(short, np.nextafter(step, np.copysign(np.float32(np.inf), step)), step)
+    assert step.dtype == np.float32
+    return res, lo32, step
+
+
 class NeuTex(nn.Module):
     def __init__(self, opt=None, primitive_type=None, sample_num=None, device='cuda', split_bf16=False, points_per_primitive=None):
         super().__init__()
@@ -332,6 +353,100 @@ class NeuTex(nn.Module):
                                                           _lib.UV_TEX_DIFFUSE if diffuse else 0, out.data_ptr(),
                                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out.view(lead + (3,))
+
+    # --- point queries and the UV-textured mesh (include/ngf.h: ngf_uv_query, ngf_uv_density_lattice) ------------------
+    def _gpu(self, what):
+        dev = torch.device(self.device)
+        if dev.type != 'cuda':
+            raise RuntimeError(f"ngf_amd NeuTex {what} on the GPU only (device='cuda'); there is no CPU path")
+        return dev
+
+    @torch.no_grad()
+    def query(self, xyz, viewdirs=None, *, want=('sigma', 'uv', 'rgb'), diffuse=False, clip=True):
+        """The model at world points ``xyz`` [..., 3]: a dict with the entries named in ``want`` --
+        ``sigma`` [...]: ``net_geometry_decoder(pts)["density"]``, exactly 0 outside the open cube (-1,1)^3 unless ``clip=False``;
+        ``uv`` [..., D] (D = 3 sphere, 2 square): ``gauge_transform(pts)``; ``rgb`` [..., 3]: ``net_texture(uv, viewdirs)`` at that uv, with
+        ``viewdirs`` one 3-vector or [..., 3], used as given, or ``diffuse=True`` for the exporters' viewdir=None colour -- bit for bit
+        ``texture_colors(uv, viewdirs)``.  A part that is not wanted does not run (``uv`` alone costs 6 % of the three).  fp32 whatever the
+        model's ``split_bf16``; a point's values do not depend on the other points or on the other entries of ``want``."""
+        dev = self._gpu("answers point queries")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in ('sigma', 'uv', 'rgb') for w in want):
+            raise ValueError(f"want must name some of 'sigma', 'uv', 'rgb', got {want!r}")
+        xyz = torch.as_tensor(xyz)
+        if xyz.shape[-1] != 3:
+            raise ValueError(f"xyz must be [..., 3], got {tuple(xyz.shape)}")
+        lead = tuple(xyz.shape[:-1])
+        pts = xyz.detach().to(dev, torch.float32).reshape(-1, 3).contiguous()
+        n = pts.shape[0]
+        view, stride = None, 0
+        if 'rgb' in want and not diffuse:
+            if viewdirs is None:
+                raise ValueError("query needs viewdirs for 'rgb' unless diffuse=True")
+            view = torch.as_tensor(viewdirs).detach().to(dev, torch.float32)
+            if view.shape[-1] != 3:
+                raise ValueError(f"viewdirs must be a 3-vector or [..., 3], got {tuple(view.shape)}")
+            if view.numel() == 3:
+                view = view.reshape(3).contiguous()
+            else:
+                view, stride = view.expand(lead + (3,)).reshape(-1, 3).contiguous(), 3
+        sigma = torch.empty((n,), device=dev) if 'sigma' in want else None
+        uv = torch.empty((n, 3), device=dev) if 'uv' in want else None
+        rgb = torch.empty((n, 3), device=dev) if 'rgb' in want else None
+        if n:
+            h = self.handle()
+            flags = (_lib.UV_TEX_DIFFUSE if diffuse else 0) | (0 if clip else _lib.UV_QUERY_NO_CLIP)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().ngf_uv_query(h, pts.data_ptr(), n, None if view is None else view.data_ptr(), stride, flags,
+                                                   None if sigma is None else sigma.data_ptr(), None if uv is None else uv.data_ptr(),
+                                                   None if rgb is None else rgb.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        out = {}
+        if sigma is not None:
+            out['sigma'] = sigma.view(lead)
+        if uv is not None:
+            D = 2 if self.primitive_type == 'square' else 3
+            out['uv'] = uv[:, :D].reshape(lead + (D,))
+        if rgb is not None:
+            out['rgb'] = rgb.view(lead + (3,))
+        return out
+
+    @torch.no_grad()
+    def density_lattice(self, resolution, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.0), clip=True):
+        """The density on the lattice of ``resolution`` (an int or a triple, >= 2 per axis) points from ``lo`` to ``hi``: ``(volume [nx,ny,nz],
+        lo, step)`` with ``step = (hi - lo) / (n - 1)`` in float32 (numpy arrays; an ulp longer where the last point would stop short of hi) and ``volume[i,j,k]`` the density at ``lo + (i,j,k) * step``,
+        every product and every sum rounded to float32 -- the layout and spacing ``mesh.marching_cubes`` takes.  The kernel generates the
+        points; with ``clip`` a lattice that reaches the faces of the cube is 0 there (``query``'s clip), so an iso-surface closes."""
+        dev = self._gpu("evaluates density lattices")
+        res, lo32, step = lattice_axes(resolution, lo, hi)
+        vol = torch.empty(res, device=dev)
+        h = self.handle()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ngf_uv_density_lattice(h, (C.c_float * 3)(*lo32.tolist()), (C.c_float * 3)(*step.tolist()), res[0], res[1], res[2],
+                                                         0 if clip else _lib.UV_QUERY_NO_CLIP, vol.data_ptr(),
+                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return vol, lo32, step
+
+    @torch.no_grad()
+    def export_mesh(self, path=None, *, level, resolution=256, viewdir=None, texture_resolution=512, normals=False, flip=False):
+        """The model's surface with its texture atlas mapped onto it -- what UV-Mapping/test.py:39-55 sketches: ``density_lattice(resolution)``,
+        marching cubes at ``level`` (no default: NeuTex densities have no natural scale), the gauge at the vertices, ``mesh.atlas_coords`` of
+        it.  Returns ``(verts [nv,3], faces [nt,3] int32, st [nv,2])`` on the device.  With ``path`` also writes ``path`` (OBJ; the sphere's
+        seam triangles get per-corner coordinates, ``mesh.unwrap_seam``), its ``.mtl`` and the atlas as ``.png``: ``_export_sphere`` /
+        ``_export_square`` at ``texture_resolution`` for ``viewdir`` (None: the diffuse texture) ``** (1/2.2)``, clamped, as 8-bit (test.py:60-88)."""
+        from . import evalout, mesh
+        self._gpu("exports meshes")
+        vol, lo, step = self.density_lattice(resolution)
+        got = mesh.marching_cubes(vol, level, spacing=step.tolist(), origin=lo.tolist(), normals=normals, flip=flip)
+        verts, faces = got[0], got[1]
+        sphere = self.primitive_type != 'square'
+        uv = self.query(verts, want=('uv',))['uv']
+        st = mesh.atlas_coords(uv, self.primitive_type, texture_resolution if sphere else None)
+        if path is not None:
+            tex = self.net_texture._export_sphere(texture_resolution, viewdir) if sphere else self.net_texture._export_square(texture_resolution, viewdir)
+            image = evalout.to_uint8((tex ** (1 / 2.2)).clamp(0, 1).contiguous()).cpu().numpy()
+            st_file, faces_vt = mesh.unwrap_seam(faces, st) if sphere else (st, None)
+            mesh.write_obj(path, verts, faces, st_file, faces_vt, texture=image, normals=got[2] if normals else None)
+        return verts, faces, st
 
     def __setstate__(self, state):
         super().__setstate__(state)
