@@ -559,12 +559,15 @@ class NeuTex(nn.Module):
         bg = None if background_color is None else background_color.detach().to(dev, torch.float32).contiguous()
         if tuple(cam.shape) != (N, 3) or (bg is not None and tuple(bg.shape) != (N, 3)):
             raise ValueError(f"camera_position / background_color must be [N,3] with N = {N}")
+        if S <= 0:
+            raise RuntimeError(f"NeuTex renders with sample_num > 0, got {S}")
         with torch.cuda.device(dev):
             st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(_lib.lib().ngf_uv_render_batch(
-                h, cam.data_ptr(), rd.data_ptr(), None if bg is None else bg.data_ptr(), U.data_ptr(), N, R, S, color.data_ptr(), trans.data_ptr(),
-                None if dbg_s is None else dbg_s.data_ptr(), None if dbg_c is None else dbg_c.data_ptr(),
-                None if stats is None else stats.data_ptr(), st))
+            if N * R > 0:          # (the tensors of an empty batch have no storage: the library would take their null pointers for missing arguments)
+                _lib.check(_lib.lib().ngf_uv_render_batch(
+                    h, cam.data_ptr(), rd.data_ptr(), None if bg is None else bg.data_ptr(), U.data_ptr(), N, R, S, color.data_ptr(), trans.data_ptr(),
+                    None if dbg_s is None else dbg_s.data_ptr(), None if dbg_c is None else dbg_c.data_ptr(),
+                    None if stats is None else stats.data_ptr(), st))
         out = {"color": color, "transmittance": trans}
         if collect_stats:
             self.last_stats = stats
