@@ -494,6 +494,27 @@ int ngf_uv_query(const ngf_uv *m, const float *xyz, int64_t n, const float *view
                  float *sigma /*[n] or NULL*/, float *uv /*[n,3] or NULL; z = 0 for square*/, float *rgb /*[n,3] or NULL*/, void *hip_stream);
 int ngf_uv_density_lattice(const ngf_uv *m, const float lo[3], const float step[3], int32_t nx, int32_t ny, int32_t nz, int32_t flags,
                            float *sigma /*[nx,ny,nz]*/, void *hip_stream);
+/* The inverse gauge: NeuTex's fourth network, inverse_gauge.inverse_network (gauge_fields.py:78-120, a modified AtlasNet core), which takes a
+ * point of the atlas template (uv in R^2 for square models, a direction in R^3 for sphere models) back to the world.  A handle of its own:
+ * five nn.Linear layers in evaluation order, reference layouts (weight [out,in], bias [out], float32, device):
+ *   [0] linear1 D-64   [1] linear2 64-512   [2..3] linear_list.{0,1} 512-512   [4] last_linear 512-3,   ReLU between them.
+ * The sizes are fixed (the reference's defaults, gauge_fields.py:83); input_dim = D is 2 or 3.  The weights are copied and packed at create.
+ * ngf_uv_inverse_map: xyz [n,3] = the network at uv [n,D], device floats, used as given (any finite input, on the template or off it).
+ *   fp32 on the matrix pipe, no bf16 form.  Asynchronous on the stream; no atomics: a point's three floats are the same bits whatever n and
+ *   the point's place in the list, and from launch to launch; nothing is written beyond xyz[3 n].  n == 0 returns NGF_OK without a launch.
+ * NGF_E_ARG, before any GPU work and before anything is dereferenced: null desc / out / handle / uv / xyz, a missing layer, input_dim
+ * outside {2, 3}, n < 0. */
+#define NGF_UV_INVERSE_LAYERS 5
+typedef struct ngf_uv_inverse_desc {
+    int32_t input_dim;
+    int32_t pad_;
+    const float *w[NGF_UV_INVERSE_LAYERS];
+    const float *b[NGF_UV_INVERSE_LAYERS];
+} ngf_uv_inverse_desc;
+typedef struct ngf_uv_inverse ngf_uv_inverse;
+int ngf_uv_inverse_create(const ngf_uv_inverse_desc *desc, ngf_uv_inverse **out, void *hip_stream);
+int ngf_uv_inverse_destroy(ngf_uv_inverse *h);
+int ngf_uv_inverse_map(const ngf_uv_inverse *h, const float *uv /*[n,D]*/, int64_t n, float *xyz /*[n,3]*/, void *hip_stream);
 /* Replaces NeuTex.forward's colour outputs for one camera (model.py:30-52):
  *   campos_host float[3], bg_host float[3] or NULL (HOST pointers), raydir [R,3], jitter_u [R,S] = the uniforms
  *   cube_ray_generation draws with torch.rand (renderer.py:112-117; jitter = 0.05 always, model.py:30);

@@ -33,7 +33,8 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_uv_train_backward", "ngf_uv_train_get_grads", "ngf_uv_train_params_changed", "ngf_uv_texture_eval", "ngf_debug_uvt_gemm",
            "ngf_debug_ii_product", "ngf_debug_ii_counts",
            "ngf_mesh_workspace_bytes", "ngf_mesh_count", "ngf_mesh_emit", "ngf_debug_mesh_scan",
-           "ngf_field_query", "ngf_uv_query", "ngf_uv_density_lattice"]
+           "ngf_field_query", "ngf_uv_query", "ngf_uv_density_lattice",
+           "ngf_uv_inverse_create", "ngf_uv_inverse_destroy", "ngf_uv_inverse_map"]
 
 
 class FieldDesc(C.Structure):
@@ -57,6 +58,13 @@ UV_LAYERS = 29
 
 class UvDesc(C.Structure):
     _fields_ = [("sphere", C.c_int32), ("flags", C.c_int32), ("w", C.c_void_p * UV_LAYERS), ("b", C.c_void_p * UV_LAYERS)]
+
+
+UV_INVERSE_LAYERS = 5
+
+
+class UvInverseDesc(C.Structure):
+    _fields_ = [("input_dim", C.c_int32), ("pad_", C.c_int32), ("w", C.c_void_p * UV_INVERSE_LAYERS), ("b", C.c_void_p * UV_INVERSE_LAYERS)]
 
 
 UV_F_SPLIT_BF16 = 1
@@ -122,6 +130,9 @@ def _load(path):
         L.ngf_uv_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngf_uv_density_lattice.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_void_p]
+        L.ngf_uv_inverse_create.argtypes = [C.POINTER(UvInverseDesc), C.POINTER(C.c_void_p), C.c_void_p]
+        L.ngf_uv_inverse_destroy.argtypes = [C.c_void_p]
+        L.ngf_uv_inverse_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ngf_pack_mask_bits.argtypes =[C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ngf_resize_bilinear.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         L.ngf_eval_workspace_bytes.restype = C.c_int64

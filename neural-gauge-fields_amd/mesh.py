@@ -1,6 +1,7 @@
 """Mesh export on the GPU: marching cubes over a dense float volume (csrc/ngf_mesh.hip), the reference's
 ``convert_sdf_samples_to_ply`` (TriPlane/utils.py:179-239) on top of it, and a binary PLY writer in numpy (there is no ``plyfile``).  For NeuTex
-(uvmapping.NeuTex.export_mesh): ``atlas_coords`` (gauge uv -> OBJ texture coordinates in the exported atlas), ``unwrap_seam`` and ``write_obj``.
+(uvmapping.NeuTex.export_mesh): ``atlas_coords`` (gauge uv -> OBJ texture coordinates in the exported atlas), ``unwrap_seam`` and ``write_obj``;
+``icosphere`` and ``square_template`` are the atlas templates of NeuTex.coordinate_deformation (numpy, on the host).
 
 The triangulation is the table of ``ngf_amd.mesh_table``: the usual one-vertex-per-crossing-edge definition, closed and consistently
 oriented, but NOT skimage's Lewiner tables -- vertex and face ORDER (and the split of a cell's polygons into triangles) differ from
@@ -195,6 +196,56 @@ def write_obj(path, verts, faces, st, faces_vt=None, texture=None, normals=None)
         parts += rows("f %d/%d %d/%d %d/%d\n", np.stack([f + 1, fv + 1], axis=-1).reshape(-1, 6))
     with open(path, "w") as fh:
         fh.write("".join(parts))
+
+
+# --- the atlas templates of NeuTex.coordinate_deformation (uvmapping.py) ------------------------------------------------
+_ICO_FACES = ((0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+              (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1))
+
+
+def icosphere(division):
+    """The unit icosphere: an icosahedron subdivided ``division`` times 4-to-1, every level normalised to the sphere (in float64; the result is
+    rounded to float32 once).  Returns ``(verts float32 [10 * 4^d + 2, 3], faces int64 [20 * 4^d, 3])`` as numpy arrays, closed, faces
+    counter-clockwise seen from outside.
+
+    The order is this project's own (there is no trimesh here to match).  Level 0: the twelve vertices (-1,t,0) (1,t,0) (-1,-t,0) (1,-t,0)
+    (0,-1,t) (0,1,t) (0,-1,-t) (0,1,-t) (t,0,-1) (t,0,1) (-t,0,-1) (-t,0,1), t the golden ratio, normalised, and the twenty faces of
+    ``_ICO_FACES``.  A level keeps the vertices it has and appends one midpoint per edge, the edges in ascending order of (smaller end, larger
+    end); face (a, b, c) becomes, in place and in this order, (a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)."""
+    d = int(division)
+    if d < 0:
+        raise ValueError(f"icosphere: division must be >= 0, got {division}")
+    t = (1.0 + np.sqrt(5.0)) / 2.0
+    v = np.array([(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+                  (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)], dtype=np.float64)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    f = np.array(_ICO_FACES, dtype=np.int64)
+    for _ in range(d):
+        nv = v.shape[0]
+        ends = np.stack([f, np.roll(f, -1, axis=1)], axis=-1)          # [F, 3, 2]: edges ab, bc, ca
+        lo, hi = ends.min(-1), ends.max(-1)
+        key, inv = np.unique(lo * nv + hi, return_inverse=True)
+        mid = v[key // nv] + v[key % nv]
+        v = np.concatenate([v, mid / np.linalg.norm(mid, axis=1, keepdims=True)], axis=0)
+        m = nv + inv.reshape(-1, 3)                                    # ab, bc, ca of every face
+        a, b, c, ab, bc, ca = f[:, 0], f[:, 1], f[:, 2], m[:, 0], m[:, 1], m[:, 2]
+        f = np.stack([a, ab, ca, b, bc, ab, c, ca, bc, ab, bc, ca], axis=-1).reshape(-1, 3)
+    return v.astype(np.float32), np.ascontiguousarray(f)
+
+
+def square_template(side):
+    """The regular grid of the reference's SquareTemplate.get_regular_points (gauge_fields.py:139-143) as a mesh: ``(verts float32 [side^2, 2],
+    faces int64 [2 (side - 1)^2, 3])`` as numpy arrays.  Vertex i * side + j is (u_i, u_j) with u = ``np.linspace(-1, 1, side)`` (float64,
+    rounded to float32 once, as the reference's ``torch.FloatTensor(uv)`` rounds it); cell (i, j), cells in row-major order, gives the two
+    triangles ((i,j), (i+1,j), (i+1,j+1)) and ((i,j), (i+1,j+1), (i,j+1)), both of positive area in the (u_0, u_1) plane."""
+    side = int(side)
+    if side < 2:
+        raise ValueError(f"square_template: side must be >= 2, got {side}")
+    uv = np.stack(np.meshgrid(*([np.linspace(-1, 1, side)] * 2), indexing="ij"), axis=-1).reshape((-1, 2))
+    i, j = np.meshgrid(np.arange(side - 1, dtype=np.int64), np.arange(side - 1, dtype=np.int64), indexing="ij")
+    p00, p10, p11, p01 = i * side + j, (i + 1) * side + j, (i + 1) * side + j + 1, i * side + j + 1
+    faces = np.stack([p00, p10, p11, p00, p11, p01], axis=-1).reshape(-1, 3)
+    return uv.astype(np.float32), np.ascontiguousarray(faces)
 
 
 def mesh_points(verts, bbox, offset=None, scale=None):

@@ -235,6 +235,24 @@ def uvmapping_params(seed=0, primitive_type="sphere", bias_std=0.05):
     return p
 
 
+def inverse_gauge_params(seed=0, primitive_type="sphere", bias_std=0.05):
+    """NeuTex's inverse network (gauge_fields.py:78-120: D -> 64 -> 512 -> 512 -> 512 -> 3, D = 3 sphere | 2 square) keyed by the reference's
+    state_dict names ``inverse_gauge.inverse_network.*``.  Xavier-uniform with the ReLU gain on the layers a ReLU follows, so that about half of
+    every hidden layer is active and the output is of order 1 (tests/golden/make_golden_uv_inverse.py checks both at capture); streams 700.. ,
+    apart from uvmapping_params' 500..557."""
+    if primitive_type not in ("sphere", "square"):
+        raise ValueError(f"Unknown primitive type {primitive_type}")
+    D = 3 if primitive_type == "sphere" else 2
+    g_relu = math.sqrt(2.0)
+    pre = "inverse_gauge.inverse_network."
+    p = {}
+    layers = (("linear1", 64, D, g_relu), ("linear2", 512, 64, g_relu), ("linear_list.0", 512, 512, g_relu), ("linear_list.1", 512, 512, g_relu),
+              ("last_linear", 3, 512, 1.0))
+    for i, (name, out_f, in_f, gain) in enumerate(layers):
+        p[pre + name + ".weight"], p[pre + name + ".bias"] = _xavier(seed, 700 + 2 * i, out_f, in_f, gain, bias_std)
+    return p
+
+
 def dtu_rays(H=600, W=800, campos=(1.7514, 0.0961, -4.7220), focal=(1446.17, 1441.59), center=(411.60, 309.54), rows=None):
     """Pin-hole rays of a DTU-like view (UV-Mapping/data/dtu.py:27-37 convention: normalised directions through
     pixel centres, camera looking at the origin).  Returns campos [3] and raydir [rows*W, 3] float32."""

@@ -18,6 +18,10 @@ Point queries: ``NeuTex.query`` (density, gauge uv, colour at world points), ``N
 ``vt`` coordinates map the exported atlas onto the marching-cubes surface) run the three MLPs on explicit points in a HIP kernel of their own
 (include/ngf.h: ngf_uv_query, ngf_uv_density_lattice).
 
+Inverse gauge: ``NeuTex.inverse_map`` (template point -> world point), ``NeuTex.cycle_error`` and ``NeuTex.coordinate_deformation`` (the
+reference's deformed-template mesh, model.py:383-418) run ``inverse_gauge.inverse_network`` in a HIP kernel of its own (include/ngf.h:
+ngf_uv_inverse_map).  ``InverseGauge.map`` stays the differentiable torch path that training uses.
+
 Training: with ``net.differentiable = True`` (an attribute, never saved) and grad enabled, ``forward`` returns the reference's training dict
 with a graph over every parameter (uv_train.py, include/ngf.h: ngf_uv_trainer_*).  Off, or under ``torch.no_grad()``, it is the eval path.
 """
@@ -175,8 +179,9 @@ class TextureMlpDecoder(nn.Module):
 
 
 class InverseNetwork(nn.Module):
-    """gauge_fields.py:78-119 (modified AtlasNet core): template point (2|3) -> 64 -> 512 -> 512 -> 512 -> xyz, ReLU.  Plain torch: at the
-    shipped configuration it sees only the template points of the origin loss."""
+    """gauge_fields.py:78-119 (modified AtlasNet core): template point (2|3) -> 64 -> 512 -> 512 -> 512 -> xyz, ReLU.  This module is the
+    differentiable torch path (training: the template points of the origin loss, ``points_inverse``); without a graph the same weights run
+    in a HIP kernel through ``NeuTex.inverse_map``."""
 
     def __init__(self, input_point_dim, mid_size=64, hidden_size=512, num_layers=2):
         super().__init__()
@@ -192,6 +197,11 @@ class InverseNetwork(nn.Module):
         for lin in self.linear_list:
             x = F.relu(lin(x))
         return self.last_linear(x)
+
+
+# the launch shape of ngf_uv_inverse_map (csrc/ngf_uv_inverse.hpp: kUvInvTilePoints, kUvInvWaves; tests/test_uv_inverse_cpu.py compares): a wave
+# pass takes 16 points, a block has four waves, the grid is capped at the CU count -- one full grid of passes is their product
+INVERSE_TILE_POINTS, INVERSE_WAVES_PER_BLOCK = 16, 4
 
 
 class InverseGauge(nn.Module):
@@ -260,6 +270,8 @@ class NeuTex(nn.Module):
         self._uv_engine = None
         self._handle = None
         self._key = None
+        self._inv_handle = None
+        self._inv_key = None
         self.to(device)
 
     def layers(self):
@@ -433,7 +445,7 @@ class NeuTex(nn.Module):
         it.  Returns ``(verts [nv,3], faces [nt,3] int32, st [nv,2])`` on the device.  With ``path`` also writes ``path`` (OBJ; the sphere's
         seam triangles get per-corner coordinates, ``mesh.unwrap_seam``), its ``.mtl`` and the atlas as ``.png``: ``_export_sphere`` /
         ``_export_square`` at ``texture_resolution`` for ``viewdir`` (None: the diffuse texture) ``** (1/2.2)``, clamped, as 8-bit (test.py:60-88)."""
-        from . import evalout, mesh
+        from . import mesh
         self._gpu("exports meshes")
         vol, lo, step = self.density_lattice(resolution)
         got = mesh.marching_cubes(vol, level, spacing=step.tolist(), origin=lo.tolist(), normals=normals, flip=flip)
@@ -442,11 +454,94 @@ class NeuTex(nn.Module):
         uv = self.query(verts, want=('uv',))['uv']
         st = mesh.atlas_coords(uv, self.primitive_type, texture_resolution if sphere else None)
         if path is not None:
-            tex = self.net_texture._export_sphere(texture_resolution, viewdir) if sphere else self.net_texture._export_square(texture_resolution, viewdir)
-            image = evalout.to_uint8((tex ** (1 / 2.2)).clamp(0, 1).contiguous()).cpu().numpy()
-            st_file, faces_vt = mesh.unwrap_seam(faces, st) if sphere else (st, None)
-            mesh.write_obj(path, verts, faces, st_file, faces_vt, texture=image, normals=got[2] if normals else None)
+            self._write_atlas_obj(path, verts, faces, st, viewdir, texture_resolution, got[2] if normals else None)
         return verts, faces, st
+
+    def _write_atlas_obj(self, path, verts, faces, st, viewdir, texture_resolution, normals=None):
+        """``path`` (OBJ), its ``.mtl`` and the atlas ``.png`` for a mesh whose texture coordinates ``st`` are ``mesh.atlas_coords`` at
+        ``texture_resolution``: the exporter's image for ``viewdir`` (None: diffuse) ``** (1/2.2)``, clamped, 8-bit; the sphere's seam unwrapped."""
+        from . import evalout, mesh
+        sphere = self.primitive_type != 'square'
+        tex = self.net_texture._export_sphere(texture_resolution, viewdir) if sphere else self.net_texture._export_square(texture_resolution, viewdir)
+        image = evalout.to_uint8((tex ** (1 / 2.2)).clamp(0, 1).contiguous()).cpu().numpy()
+        st_file, faces_vt = mesh.unwrap_seam(faces, st) if sphere else (st, None)
+        mesh.write_obj(path, verts, faces, st_file, faces_vt, texture=image, normals=normals)
+
+    # --- the inverse gauge on the GPU (include/ngf.h: ngf_uv_inverse_map; DESIGN.md section 4.12) -------------------------------------------
+    def inverse_layers(self):
+        """The five Linear layers of the inverse network in the order of ngf_uv_inverse_desc."""
+        n = self.inverse_gauge.inverse_network
+        return [n.linear1, n.linear2, n.linear_list[0], n.linear_list[1], n.last_linear]
+
+    def inverse_handle(self):
+        """The packed inverse network (ngf_uv_inverse), rebuilt when a parameter of it was written in place or replaced -- ``handle()``'s key."""
+        key = tuple((t.data_ptr(), t._version) for lin in self.inverse_layers() for t in (lin.weight, lin.bias))
+        if self._inv_handle is not None and key == self._inv_key:
+            return self._inv_handle
+        dev = self._gpu("runs the inverse gauge")
+        d = _lib.UvInverseDesc()
+        d.input_dim = self.inverse_gauge.input_point_dim
+        keep = []
+        for i, lin in enumerate(self.inverse_layers()):
+            w = lin.weight.detach().to(dev, torch.float32).contiguous()
+            b = lin.bias.detach().to(dev, torch.float32).contiguous()
+            keep += [w, b]
+            d.w[i], d.b[i] = w.data_ptr(), b.data_ptr()
+        out = C.c_void_p()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ngf_uv_inverse_create(C.byref(d), C.byref(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self._release_inverse()
+        self._inv_handle, self._inv_key = out, key
+        return out
+
+    @torch.no_grad()
+    def inverse_map(self, uv):
+        """``inverse_gauge.map(uv)`` without a graph, in a HIP kernel: template points ``uv`` [..., D] (D = 2 square, 3 sphere), used as given
+        -- on the template or off it -- -> world points [..., 3] on the model's device.  fp32 on the matrix pipe; a point's value does not
+        depend on the other points, on their number or on its place among them."""
+        dev = self._gpu("runs the inverse gauge")
+        uv = torch.as_tensor(uv)
+        D = self.inverse_gauge.input_point_dim
+        if uv.dim() < 1 or uv.shape[-1] != D:
+            raise ValueError(f"uv must be [..., {D}] for a {self.primitive_type} model, got {tuple(uv.shape)}")
+        lead = tuple(uv.shape[:-1])
+        pts = uv.detach().to(dev, torch.float32).reshape(-1, D).contiguous()
+        n = pts.shape[0]
+        out = torch.empty((n, 3), device=dev)
+        if n:
+            h = self.inverse_handle()
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().ngf_uv_inverse_map(h, pts.data_ptr(), n, out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out.view(lead + (3,))
+
+    @torch.no_grad()
+    def cycle_error(self, xyz):
+        """``|inverse_map(gauge(xyz)) - xyz|^2`` [...] at world points ``xyz`` [..., 3]: the quantity behind the reference's
+        ``loss_inverse_mapping`` (without its weights), as two launches -- ``query(xyz, want='uv')``, then ``inverse_map``."""
+        dev = self._gpu("runs the inverse gauge")
+        xyz = torch.as_tensor(xyz).detach().to(dev, torch.float32)
+        back = self.inverse_map(self.query(xyz, want=('uv',))['uv'])
+        return ((back - xyz) ** 2).sum(-1)
+
+    @torch.no_grad()
+    def coordinate_deformation(self, path=None, *, viewdir=(0, 0, 1), icosphere_division=6, side=257, texture_resolution=512):
+        """model.py:383-418 made runnable: the atlas template -- ``mesh.icosphere(icosphere_division)`` for a sphere model,
+        ``mesh.square_template(side)`` for a square model -- pushed through the inverse gauge.  Returns ``(verts [nv,3] = inverse_map(template),
+        faces [nt,3] int64, colors [nv,3] = texture_colors(template, viewdir), raw as the reference returns them, st [nv,2] =
+        mesh.atlas_coords(template))`` on the device.  With ``path`` also writes the OBJ, its ``.mtl`` and the atlas ``.png`` as ``export_mesh``
+        does.  (The reference's square branch takes trimesh's Loop-subdivided box, whose vertices this project cannot restate without
+        trimesh; the regular grid of SquareTemplate.get_regular_points is the template here.)"""
+        from . import mesh
+        dev = self._gpu("deforms templates")
+        sphere = self.primitive_type != 'square'
+        tv, tf = mesh.icosphere(icosphere_division) if sphere else mesh.square_template(side)
+        template, faces = torch.from_numpy(tv).to(dev), torch.from_numpy(tf).to(dev)
+        verts = self.inverse_map(template)
+        colors = self.texture_colors(template, viewdir)
+        st = mesh.atlas_coords(template, self.primitive_type, texture_resolution if sphere else None)
+        if path is not None:
+            self._write_atlas_obj(path, verts, faces, st, viewdir, texture_resolution)
+        return verts, faces, colors, st
 
     def __setstate__(self, state):
         super().__setstate__(state)
@@ -456,6 +551,12 @@ class NeuTex(nn.Module):
         if self._handle is not None:
             _lib.lib().ngf_uv_destroy(self._handle)
             self._handle, self._key = None, None
+        self._release_inverse()
+
+    def _release_inverse(self):
+        if getattr(self, '_inv_handle', None) is not None:
+            _lib.lib().ngf_uv_inverse_destroy(self._inv_handle)
+            self._inv_handle, self._inv_key = None, None
 
     def __del__(self):
         try:
@@ -483,7 +584,8 @@ class NeuTex(nn.Module):
         out = C.c_void_p()
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().ngf_uv_create(C.byref(d), C.byref(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        self.release()
+        if self._handle is not None:          # (the render handle alone: the inverse network's has its own key)
+            _lib.lib().ngf_uv_destroy(self._handle)
         self._handle, self._key = out, key
         self._push_texture()
         return out
