@@ -515,6 +515,33 @@ typedef struct ngf_uv_inverse ngf_uv_inverse;
 int ngf_uv_inverse_create(const ngf_uv_inverse_desc *desc, ngf_uv_inverse **out, void *hip_stream);
 int ngf_uv_inverse_destroy(ngf_uv_inverse *h);
 int ngf_uv_inverse_map(const ngf_uv_inverse *h, const float *uv /*[n,D]*/, int64_t n, float *xyz /*[n,3]*/, void *hip_stream);
+/* The same network with a backward pass (additive, ABI 5): the device side of a differentiable InverseGauge for batches of up to max_points.
+ * Unlike ngf_uv_inverse the trainer keeps the caller's ten tensors (desc: DEVICE, reference layouts, alive for the handle's life) and packs them
+ * ON THE DEVICE at the first forward after create / params_changed: the forward layouts of ngf_uv_inverse, bit for bit, and their transposes
+ * for the backward.  Nothing on this path reads back through the host.
+ * forward : xyz [n,3] = the same bits ngf_uv_inverse_map gives for these weights; keeps relu(output) of the four hidden layers, row-major.
+ * backward: d_xyz [n,3] (DEVICE) of the forward named by `ticket` -> the ten gradients, left in the trainer, and d_uv [n,D] when not NULL.
+ *           A ticket that is not the trainer's last forward returns NGF_E_STALE (run the forward again).  dX is one fused kernel per 16-point
+ *           tile; dW = dZ^T H over row chunks whose size depends on n alone (1024 rows up to 65 536 points, then n / 64 rounded up to 16),
+ *           summed in chunk order, db in fp64.  No float atomics: two backwards of one forward are the same bits.  uv must stay alive and
+ *           unchanged between the two calls only if the caller wants to run the forward again.
+ * get_grads copies every wanted gradient (order: weight, bias of layers 0..4; NULL = skip); NGF_E_ARG if no backward ran since the last forward.
+ * NGF_E_ARG, before any GPU work and before anything is dereferenced: null desc / out / handle / ticket / d_xyz, null uv / xyz with n > 0, a missing
+ * layer, input_dim outside {2, 3}, max_points outside 1 .. 2^27 - 1, n < 0, n > max_points.  n == 0 is NGF_OK without a launch (its backward gives
+ * zero gradients).  Asynchronous on hip_stream; a trainer must not be used from two streams at once.
+ * (backward needs d_xyz non-NULL also after a forward of n == 0; forward takes NULL uv / xyz at n == 0.)
+ * Profiling aid: ngf_debug_uv_inverse_train_dx is the backward's dX chain alone -- same arguments and checks, every layer's dZ and d_uv are
+ * written, no weight gradient is computed and none is left (get_grads refuses until the next full backward). */
+#define NGF_UV_INVERSE_TRAIN_PARAMS (2 * NGF_UV_INVERSE_LAYERS)
+typedef struct ngf_uv_inverse_trainer ngf_uv_inverse_trainer;
+int ngf_uv_inverse_trainer_create(const ngf_uv_inverse_desc *desc, int64_t max_points, ngf_uv_inverse_trainer **out, void *hip_stream);
+int ngf_uv_inverse_trainer_destroy(ngf_uv_inverse_trainer *t);
+int64_t ngf_uv_inverse_trainer_bytes(const ngf_uv_inverse_trainer *t);
+int ngf_uv_inverse_train_params_changed(ngf_uv_inverse_trainer *t);
+int ngf_uv_inverse_train_forward(ngf_uv_inverse_trainer *t, const float *uv /*[n,D]*/, int64_t n, float *xyz /*[n,3]*/, int64_t *ticket, void *hip_stream);
+int ngf_uv_inverse_train_backward(ngf_uv_inverse_trainer *t, int64_t ticket, const float *d_xyz /*[n,3]*/, float *d_uv /*[n,D] or NULL*/, void *hip_stream);
+int ngf_uv_inverse_train_get_grads(ngf_uv_inverse_trainer *t, float *const out[NGF_UV_INVERSE_TRAIN_PARAMS], void *hip_stream);
+int ngf_debug_uv_inverse_train_dx(ngf_uv_inverse_trainer *t, int64_t ticket, const float *d_xyz /*[n,3]*/, float *d_uv /*[n,D] or NULL*/, void *hip_stream);
 /* Replaces NeuTex.forward's colour outputs for one camera (model.py:30-52):
  *   campos_host float[3], bg_host float[3] or NULL (HOST pointers), raydir [R,3], jitter_u [R,S] = the uniforms
  *   cube_ray_generation draws with torch.rand (renderer.py:112-117; jitter = 0.05 always, model.py:30);

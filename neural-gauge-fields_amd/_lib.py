@@ -34,7 +34,9 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_debug_ii_product", "ngf_debug_ii_counts",
            "ngf_mesh_workspace_bytes", "ngf_mesh_count", "ngf_mesh_emit", "ngf_debug_mesh_scan",
            "ngf_field_query", "ngf_uv_query", "ngf_uv_density_lattice",
-           "ngf_uv_inverse_create", "ngf_uv_inverse_destroy", "ngf_uv_inverse_map"]
+           "ngf_uv_inverse_create", "ngf_uv_inverse_destroy", "ngf_uv_inverse_map",
+           "ngf_uv_inverse_trainer_create", "ngf_uv_inverse_trainer_destroy", "ngf_uv_inverse_trainer_bytes", "ngf_uv_inverse_train_params_changed",
+           "ngf_uv_inverse_train_forward", "ngf_uv_inverse_train_backward", "ngf_uv_inverse_train_get_grads", "ngf_debug_uv_inverse_train_dx"]
 
 
 class FieldDesc(C.Structure):

@@ -38,6 +38,7 @@ struct UvInverseArgs {
     int32_t w1, b1, w2, b2, wh, bh, wo, bo;      // wh / bh: the two hidden layers, strides 512 * 512 / 512
 };
 
+#ifndef NGF_UV_INVERSE_NO_KERNEL      // (ngf_uv_inverse_train.hpp takes the constants and the argument block; the kernel stays in ONE unit)
 __global__ void __launch_bounds__(64 * kUvInvWaves) uv_inverse_kernel(const UvInverseArgs Q)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -87,5 +88,6 @@ __global__ void __launch_bounds__(64 * kUvInvWaves) uv_inverse_kernel(const UvIn
         }
     }
 }
+#endif
 
 }  // namespace ngf

@@ -4,8 +4,8 @@ reference's own loop uses it (UV-Mapping/train.py:138-141, model.py:300-356) -- 
 ``UvGrad`` is the device engine (include/ngf.h, ngf_uv_trainer_*): ``forward`` renders the batch with the trainer's kernels and keeps every layer's
 activations, ``backward`` takes d loss / d (color, transmittance, uv, blend weight) and returns the gradients of the 58 render-layer tensors in
 their reference layouts.  ``_UvRender`` is the torch.autograd.Function around it; ``uvmapping.NeuTex`` owns one engine when ``net.differentiable``
-is set.  In training the inverse network (``inverse_gauge``) stays plain torch: it sees the template points and, with an inverse-mapping loss,
-``uv``; its HIP kernel (``NeuTex.inverse_map``) is a forward without a graph."""
+is set.  The inverse network (``inverse_gauge``) sees the template points and, with an inverse-mapping loss, ``uv``: plain torch by default,
+its own HIP forward and backward with ``net.inverse_gauge.differentiable = True`` (uv_inverse_train.py)."""
 from __future__ import annotations
 
 import ctypes as C

@@ -20,7 +20,10 @@ Point queries: ``NeuTex.query`` (density, gauge uv, colour at world points), ``N
 
 Inverse gauge: ``NeuTex.inverse_map`` (template point -> world point), ``NeuTex.cycle_error`` and ``NeuTex.coordinate_deformation`` (the
 reference's deformed-template mesh, model.py:383-418) run ``inverse_gauge.inverse_network`` in a HIP kernel of its own (include/ngf.h:
-ngf_uv_inverse_map).  ``InverseGauge.map`` stays the differentiable torch path that training uses.
+ngf_uv_inverse_map).  They build no graph.  With ``net.inverse_gauge.differentiable = True`` (an attribute, never saved),
+grad enabled and the parameters on a GPU, ``InverseGauge.forward`` and ``InverseGauge.map`` -- the origin loss's template points and
+``points_inverse`` -- run the same network forwards and backwards on HIP kernels too (uv_inverse_train.py, include/ngf.h:
+ngf_uv_inverse_trainer_*); otherwise they are plain torch.
 
 Training: with ``net.differentiable = True`` (an attribute, never saved) and grad enabled, ``forward`` returns the reference's training dict
 with a graph over every parameter (uv_train.py, include/ngf.h: ngf_uv_trainer_*).  Off, or under ``torch.no_grad()``, it is the eval path.
@@ -180,8 +183,8 @@ class TextureMlpDecoder(nn.Module):
 
 class InverseNetwork(nn.Module):
     """gauge_fields.py:78-119 (modified AtlasNet core): template point (2|3) -> 64 -> 512 -> 512 -> 512 -> xyz, ReLU.  This module is the
-    differentiable torch path (training: the template points of the origin loss, ``points_inverse``); without a graph the same weights run
-    in a HIP kernel through ``NeuTex.inverse_map``."""
+    torch path of training (the template points of the origin loss, ``points_inverse``); with ``InverseGauge.differentiable`` set the same
+    weights train through HIP kernels (uv_inverse_train.py), and without a graph they run in one through ``NeuTex.inverse_map``."""
 
     def __init__(self, input_point_dim, mid_size=64, hidden_size=512, num_layers=2):
         super().__init__()
@@ -227,12 +230,57 @@ class InverseGauge(nn.Module):
 
     def forward(self, template_points=None):
         pts = self.random_points(self.num_points_per_primitive) if template_points is None else template_points
+        if self._on_kernels() and pts.numel():          # (an empty batch is torch's: same empty result, same graph, no engine)
+            return pts, self._map_hip('_template_engine', pts).view(1, 1, -1, 3)
         return pts, self.inverse_network(pts.unsqueeze(0)).unsqueeze(1).contiguous()
 
     def map(self, uv):
         assert uv.shape[-1] == self.input_point_dim
+        if self._on_kernels() and uv.numel():
+            return self._map_hip('_map_engine', uv).view(uv.shape[:-1] + (3,))
         out = self.inverse_network(uv.reshape(-1, self.input_point_dim))
         return out.view(uv.shape[:-1] + (3,))
+
+    # --- training on the HIP kernels (uv_inverse_train.py) ---------------------------------------------------
+    differentiable = False          # training switch, as NeuTex.differentiable: a plain attribute, never saved
+    _template_engine = None         # one engine per call site: the template points of ``forward`` and the uv of ``map`` meet in one
+    _map_engine = None              # iteration, and a shared engine would make each other's tickets stale (a third forward per step)
+
+    def _on_kernels(self):
+        """``differentiable`` set, grad enabled and the parameters on a GPU; else ``forward`` and ``map`` are the torch code above."""
+        return self.differentiable and torch.is_grad_enabled() and self.inverse_network.linear1.weight.is_cuda
+
+    def _inverse_engine(self, attr, n):
+        from .uv_inverse_train import InverseGrad, inverse_params
+        return _engine.grad_engine(self, attr, InverseGrad, inverse_params(self), int(n), 1)
+
+    def _map_hip(self, attr, pts):
+        from .uv_inverse_train import _InverseMap
+        dev = self.inverse_network.linear1.weight.device
+        x = pts.to(dev, torch.float32).reshape(-1, self.input_point_dim).contiguous()
+        eng = self._inverse_engine(attr, x.shape[0])
+        return _InverseMap.apply(self, attr, eng, x, *eng.params)
+
+    def inverse_grad_engines(self):
+        """The training engines (uv_inverse_train.InverseGrad: max_rays = points, bytes, forwards) of ``forward`` and ``map``, or None each."""
+        return self._template_engine, self._map_engine
+
+    def release_inverse_grad_engines(self):
+        """Free both engines' per-point buffers (the next differentiable call builds a new one)."""
+        _engine.release_engine(self, '_template_engine')
+        _engine.release_engine(self, '_map_engine')
+
+    def __getstate__(self):              # engines are not state: not pickled, not deep-copied (they are not in state_dict either)
+        d = self.__dict__.copy()
+        d.pop('_template_engine', None)
+        d.pop('_map_engine', None)
+        return d
+
+    def __del__(self):
+        try:
+            self.release_inverse_grad_engines()
+        except Exception:
+            pass
 
 
 def lattice_axes(resolution, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.0)):
@@ -552,6 +600,7 @@ class NeuTex(nn.Module):
             _lib.lib().ngf_uv_destroy(self._handle)
             self._handle, self._key = None, None
         self._release_inverse()
+        self.inverse_gauge.release_inverse_grad_engines()
 
     def _release_inverse(self):
         if getattr(self, '_inv_handle', None) is not None:
