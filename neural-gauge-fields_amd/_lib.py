@@ -69,6 +69,16 @@ class UvInverseDesc(C.Structure):
     _fields_ = [("input_dim", C.c_int32), ("pad_", C.c_int32), ("w", C.c_void_p * UV_INVERSE_LAYERS), ("b", C.c_void_p * UV_INVERSE_LAYERS)]
 
 
+def uv_inverse_desc(input_dim, tensors):
+    """A UvInverseDesc over ten tensors -- weight, bias of each layer in ``InverseGauge.layers()`` order (contiguous float32 on one GPU; the
+    caller keeps them alive while the descriptor is in use)."""
+    d = UvInverseDesc()
+    d.input_dim = int(input_dim)
+    for i in range(UV_INVERSE_LAYERS):
+        d.w[i], d.b[i] = tensors[2 * i].data_ptr(), tensors[2 * i + 1].data_ptr()
+    return d
+
+
 UV_F_SPLIT_BF16 = 1
 UV_TEX_DIFFUSE = 1          # ngf_uv_texture_eval / ngf_uv_query flags
 UV_QUERY_NO_CLIP = 2        # ngf_uv_query / ngf_uv_density_lattice flags

@@ -57,6 +57,9 @@ int poison_alloc(void *p, size_t bytes, hipStream_t st);     // no-op unless kno
 
 namespace ngf {
 
+// grid size of n items at b per block, at least one block
+inline unsigned blocks(int64_t n, int b = 256) { return (unsigned)std::max<int64_t>(1, (n + b - 1) / b); }
+
 // Scoped switch to the device a handle / a parked buffer lives on (hipFree, hipMalloc and events act on the calling thread's CURRENT device).
 struct DeviceScope {
     int prev = -1;

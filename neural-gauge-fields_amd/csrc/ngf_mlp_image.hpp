@@ -50,10 +50,8 @@ inline void split3(float x, uint16_t out[3])
     out[2] = f2bf(r2);
 }
 
-// v_mfma_f32_16x16x4_f32, lane (s, kq): the hidden unit of accumulator (mt, r).  A lane's 16 ReLU'd accumulators are the next layer's B
-// operands in place, so the next layer's j-th input of lane quarter kq is unit hidden(j >> 2, j & 3, kq).
-inline int hidden(int mt, int r, int kq) { return mt * 16 + 4 * kq + r; }
-// the same for the 32-row tiles of InfoInv's density MLP, lane (i, hi): the unit of the lane half's k-th accumulator
+// hidden(mt, r, kq), the accumulator order of the 16-row tiles, is ngf_mlp_layout.hpp's (the device packer of ngf_uv_pack.hpp calls it too).
+// The same for the 32-row tiles of InfoInv's density MLP, lane (i, hi): the unit of the lane half's k-th accumulator
 inline int dens_hidden(int k, int hi) { return (k & 3) + 8 * (k >> 2) + 4 * hi; }
 
 // ---- the blocks ------------------------------------------------------------------------------------------------------------------------

@@ -14,6 +14,10 @@
 namespace ngf {
 
 // ---- ngf_shade16.hpp: v_mfma_f32_16x16x4_f32, lane (s = l & 15, kq = l >> 4) ---------------------------------------------------------
+// The hidden unit of accumulator (mt, r) of lane quarter kq.  A lane's 16 ReLU'd accumulators are the next layer's B operands in place, so the
+// next layer's j-th input of lane quarter kq is unit hidden(j >> 2, j & 3, kq).
+NGF_LAYOUT_HD int hidden(int mt, int r, int kq) { return mt * 16 + 4 * kq + r; }
+
 template <int APP>
 struct MlpLayout16 {                      // floats
     static constexpr int QCH = APP / 4;           // colour channels per plane per lane (12)

@@ -1,7 +1,8 @@
 // ngf_uv.hip -- C ABI (include/ngf.h), UV-Mapping (NeuTex) part: weight packing, render, texture editing.
 #include "ngf_host.hpp"
-#include "ngf_mlp_image.hpp"      // split3, hidden: shared with the field images
+#include "ngf_mlp_image.hpp"      // split3: shared with the field images
 #include "ngf_uv.hpp"
+#include "ngf_uv_pack.hpp"        // the slot map of the fp32 images
 
 using namespace ngf;
 
@@ -30,35 +31,29 @@ extern "C" int ngf_uv_destroy(ngf_uv *m)
 namespace {
 struct UvPacker {
     std::vector<float> buf;
-    static int hidden(int t, int kq) { return ngf::hidden(t >> 2, t & 3, kq); }      // the previous layer's unit behind k-step t of lane quarter kq
+    static int hidden(int t, int kq) { return uv_pack_input(t, kq, true); }      // the previous layer's unit behind k-step t of lane quarter kq
     int align() { while (buf.size() & 3) buf.push_back(0.0f); return (int)buf.size(); }
+    static float weight(const std::vector<float> &W, int out_f, int in_f, int o, int i) { return (o < out_f && i >= 0 && i < in_f) ? W[(size_t)o * in_f + i] : 0.0f; }
+    // an fp32 image of `count` words: ngf_uv_pack.hpp's slot map says whose each word is, value(slot) what it holds
+    template <typename F>
+    int image(int kind, int NT, size_t count, F value)
+    {
+        const int off = align();
+        buf.resize(off + count, 0.0f);
+        for (size_t idx = 0; idx < count; ++idx) buf[off + idx] = value(uv_pack_slot(kind, NT, (int)idx));
+        return off;
+    }
     // imap(t, kq) -> input index (or -1); KT k-steps; NT unit tiles (multiple of 4)
     template <typename F>
     int dense(const std::vector<float> &W, int out_f, int in_f, int KT, int NT, F imap)
     {
-        const int off = align();
-        buf.resize(off + (size_t)KT * NT * 64, 0.0f);
-        for (int t = 0; t < KT; ++t)
-            for (int g = 0; g < NT / 4; ++g)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 4; ++e) {
-                        const int o = (4 * g + e) * 16 + (l & 15), i = imap(t, l >> 4);
-                        buf[off + (((size_t)t * (NT / 4) + g) * 64 + l) * 4 + e] = (o < out_f && i >= 0 && i < in_f) ? W[(size_t)o * in_f + i] : 0.0f;
-                    }
-        return off;
+        return image(kUvPackDense, NT, (size_t)KT * NT * 64, [&](UvPackSlot s) { return weight(W, out_f, in_f, s.o, imap(s.t, s.kq)); });
     }
-    // output layer with <= 3 units: [KT / 4][64 lanes][4] -- a lane's A operands of four k-steps in one 16-byte load (dense_out)
+    // output layer with <= 3 units: a lane's A operands of four k-steps in one 16-byte load (dense_out)
     template <typename F>
     int out_layer(const std::vector<float> &W, int out_f, int in_f, int KT, F imap)
     {
-        const int off = align();
-        buf.resize(off + (size_t)KT * 64, 0.0f);
-        for (int t = 0; t < KT; ++t)
-            for (int l = 0; l < 64; ++l) {
-                const int o = l & 15, i = imap(t, l >> 4);
-                buf[off + ((size_t)(t >> 2) * 64 + l) * 4 + (t & 3)] = (o < out_f && i >= 0 && i < in_f) ? W[(size_t)o * in_f + i] : 0.0f;
-            }
-        return off;
+        return image(kUvPackOut, 0, (size_t)KT * 64, [&](UvPackSlot s) { return weight(W, out_f, in_f, s.o, imap(s.t, s.kq)); });
     }
     // split-bf16 image of a 256-unit layer: [KB][4 groups][3 parts][4 tiles][64 lanes][8 bf16]; imap(j, kq) = input index of the lane
     // quarter's j-th input (j = 8 kb + e), as in dense()
@@ -84,21 +79,11 @@ struct UvPacker {
     }
     int bias(const std::vector<float> &b, int out_f, int NT)
     {
-        const int off = align();
-        buf.resize(off + (size_t)NT * 16, 0.0f);
-        for (int kq = 0; kq < 4; ++kq)
-            for (int mt = 0; mt < NT; ++mt)
-                for (int r = 0; r < 4; ++r) {
-                    const int o = mt * 16 + 4 * kq + r;
-                    buf[off + kq * (NT * 4) + mt * 4 + r] = o < out_f ? b[o] : 0.0f;
-                }
-        return off;
+        return image(kUvPackBias, NT, (size_t)NT * 16, [&](UvPackSlot s) { return s.o < out_f ? b[s.o] : 0.0f; });
     }
     int bias4(const std::vector<float> &b, int out_f)
     {
-        const int off = align();
-        for (int e = 0; e < 4; ++e) buf.push_back(e < out_f ? b[e] : 0.0f);
-        return off;
+        return image(kUvPackBias4, 0, 4, [&](UvPackSlot s) { return s.o < out_f ? b[s.o] : 0.0f; });
     }
 };
 }  // namespace

@@ -18,11 +18,12 @@
 // and the weights alone -- a column of the matrix instructions -- so they are the same bits for every n and every place in the list.
 #pragma once
 #define NGF_UV_NO_EDIT_KERNEL
+#include "ngf_host.hpp"
 #include "ngf_uv.hpp"
+#include "ngf_uv_pack.hpp"      // kUvInvMid / kUvInvHidden / kUvInvHiddenLayers, the offsets into the packed set
 
 namespace ngf {
 
-constexpr int kUvInvMid = 64, kUvInvHidden = 512, kUvInvHiddenLayers = 2;      // fixed, as gauge_fields.py:83 fixes them
 constexpr int kUvInvTilePoints = 16;                                          // points per wave pass
 constexpr int kUvInvWaves = 4;                                                // waves per block, one per SIMD
 constexpr int kUvInvRows = kUvInvHidden / 4;                                  // LDS rows (k-steps) of a wave: 128 x 64 lanes x 4 B = 32 KB
@@ -30,16 +31,34 @@ constexpr int kUvInvWaveLds = kUvInvRows * 64;                                //
 static_assert(kUvInvRows <= 256, "store_act's ds_write2st64 offsets are 8 bits");
 
 struct UvInverseArgs {
-    const float *w;        // packed weights / biases (offsets below, floats)
+    const float *w;        // packed weights / biases (offsets in `at`, floats)
     const float *uv;       // [n, D]
     float *xyz;            // [n, 3]
     int64_t n;
     int32_t dim;           // D
-    int32_t w1, b1, w2, b2, wh, bh, wo, bo;      // wh / bh: the two hidden layers, strides 512 * 512 / 512
+    UvInvFwdAt at;
 };
 
-#ifndef NGF_UV_INVERSE_NO_KERNEL      // (ngf_uv_inverse_train.hpp takes the constants and the argument block; the kernel stays in ONE unit)
-__global__ void __launch_bounds__(64 * kUvInvWaves) uv_inverse_kernel(const UvInverseArgs Q)
+// relu(acc) of a live lane's point to its row-major row (row: the point's row + 4 kq)
+template <int NT>
+__device__ __forceinline__ void uvit_keep(float *row, bool live, const f32x4 acc[1][NT])
+{
+    if (live) {
+#pragma unroll
+        for (int mt = 0; mt < NT; ++mt) {
+            f32x4 v;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = act_fn<0>(acc[0][mt][r]);
+            *reinterpret_cast<f32x4 *>(row + mt * 16) = v;
+        }
+    }
+}
+
+// The whole pass of a block, for the inference kernel (ngf_uv_inverse.hip: uv_inverse_kernel) and the training forward
+// (ngf_uv_inverse_train.hpp: uvit_forward_kernel, KEEP): the latter also stores the POST-activation outputs of the four hidden layers,
+// row-major, to keep[0] [n, 64] and keep[1..3] [n, 512].  The arithmetic is one text, so the two kernels give the same bits.
+template <bool KEEP>
+__device__ __forceinline__ void uv_inverse_pass(const UvInverseArgs &Q, float *const *keep)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int lane = threadIdx.x & 63;
@@ -52,7 +71,8 @@ __global__ void __launch_bounds__(64 * kUvInvWaves) uv_inverse_kernel(const UvIn
         const float *W = Q.w + wz;
         const int kq = lane >> 4;
         const int64_t idx = p * kUvInvTilePoints + (lane & 15);
-        const int64_t i = idx < Q.n ? idx : Q.n - 1;          // a tail's padding lanes evaluate the last point again; nothing of theirs is stored
+        const bool live = idx < Q.n;
+        const int64_t i = live ? idx : Q.n - 1;          // a tail's padding lanes evaluate the last point again; nothing of theirs is stored
         // linear1's inputs in natural order: entry f of a point lives in row f >> 2, lane quarter f & 3.  Quarter kq supplies coordinate kq in
         // row 0; the rest of the layer's 16 padded inputs are zero.  Every lane writes its own slots only.  (No lane-dependent control flow:
         // quarter 3 -- and quarter 2 of a square model -- loads the point's last coordinate and selects the zero.)
@@ -60,34 +80,59 @@ __global__ void __launch_bounds__(64 * kUvInvWaves) uv_inverse_kernel(const UvIn
         const float xc = Q.uv[i * Q.dim + kc];
         const float x = kq < Q.dim ? xc : 0.0f;
         KStepA<32, 1> pre[4];
-        uv_wprefetch<32, 1>(W + Q.w2, lane, pre);
+        uv_wprefetch<32, 1>(W + Q.at.w2, lane, pre);
         act[lane] = x;
 #pragma unroll
         for (int t = 1; t < 4; ++t) act[t * 64 + lane] = 0.0f;
         f32x4 h4[1][4], h[1][32];
-        dense<4, 1, true>(W + Q.w1, W + Q.b1, 4, lane, act, h4);
+        dense<4, 1, true>(W + Q.at.w1, W + Q.at.b1, 4, lane, act, h4);
         store_act<4, 1, kUvActNone>(act, lane, h4);
-        dense<32, 1, true, 0>(W + Q.w2, W + Q.b2, kUvInvMid / 4, lane, act, h, 1 << 30, pre, true);
+        if constexpr (KEEP) uvit_keep<4>(keep[0] + idx * kUvInvMid + 4 * kq, live, h4);
+        dense<32, 1, true, 0>(W + Q.at.w2, W + Q.at.b2, kUvInvMid / 4, lane, act, h, 1 << 30, pre, true);
 #pragma unroll 1
         for (int l = 0; l < kUvInvHiddenLayers; ++l) {
-            const float *wl = W + Q.wh + (size_t)l * (kUvInvHidden * kUvInvHidden);
+            const float *wl = W + Q.at.wh + (size_t)l * (kUvInvHidden * kUvInvHidden);
             uv_wprefetch<32, 1>(wl, lane, pre);
             store_act<32, 1, kUvActNone>(act, lane, h);
-            dense<32, 1, true, 0>(wl, W + Q.bh + l * kUvInvHidden, kUvInvRows, lane, act, h, 1 << 30, pre, true);
+            if constexpr (KEEP) uvit_keep<32>(keep[1 + l] + idx * kUvInvHidden + 4 * kq, live, h);
+            dense<32, 1, true, 0>(wl, W + Q.at.bh + l * kUvInvHidden, kUvInvRows, lane, act, h, 1 << 30, pre, true);
         }
         UvOutW<kUvInvRows> ow;
         store_act<32, 1, kUvActNone>(act, lane, h);
-        out_prefetch<kUvInvRows>(W + Q.wo, lane, ow);
+        out_prefetch<kUvInvRows>(W + Q.at.wo, lane, ow);
+        if constexpr (KEEP) uvit_keep<32>(keep[1 + kUvInvHiddenLayers] + idx * kUvInvHidden + 4 * kq, live, h);
         __builtin_amdgcn_sched_barrier(0);
         f32x4 o[1];
-        dense_out<1, kUvInvRows, 0, true>(ow, W + Q.bo, lane, act, o);
+        dense_out<1, kUvInvRows, 0, true>(ow, W + Q.at.bo, lane, act, o);
         // the four lanes of a point hold the same values: quarter 0 stores them
-        if (lane < 16 && idx < Q.n) {
+        if (lane < 16 && live) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) Q.xyz[idx * 3 + k] = o[0][k];
         }
     }
 }
-#endif
+
+// ---- host side, shared by ngf_uv_inverse.hip and ngf_uv_inverse_train.hip ---------------------------------------------------------------------
+// `who`: the ABI function the message names
+inline int check_inverse_desc(const char *who, const ngf_uv_inverse_desc *d)
+{
+    if (d->input_dim != 2 && d->input_dim != 3) return fail(NGF_E_ARG, "%s: input_dim must be 2 (square) or 3 (sphere), got %d", who, d->input_dim);
+    for (int l = 0; l < NGF_UV_INVERSE_LAYERS; ++l)
+        if (!d->w[l] || !d->b[l]) return fail(NGF_E_ARG, "%s: layer %d missing", who, l);
+    return NGF_OK;
+}
+
+// One of the tile kernels (uv_inverse_kernel, uvit_forward_kernel, uvit_dx_kernel) over n points: four waves per block, one per SIMD, 16 points
+// per wave pass; one block per CU (128 KB of activation rows), the grid capped at the CU count.
+template <typename Args>
+inline int launch_inverse_tiles(void (*kernel)(Args), const Args &args, int64_t n, int num_cus, hipStream_t st)
+{
+    if (int rc = poison_lds(st)) return rc;
+    const int64_t grid = std::min<int64_t>(((n + kUvInvTilePoints - 1) / kUvInvTilePoints + kUvInvWaves - 1) / kUvInvWaves, num_cus);
+    const size_t lds = (size_t)kUvInvWaves * kUvInvWaveLds * sizeof(float);
+    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), lds));
+    NGF_LAUNCH(kernel, dim3((unsigned)grid), dim3(64 * kUvInvWaves), lds, st, args);
+    return NGF_OK;
+}
 
 }  // namespace ngf

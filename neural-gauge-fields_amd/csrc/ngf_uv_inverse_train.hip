@@ -7,16 +7,14 @@ using namespace ngf;
 
 namespace {
 constexpr int NL = NGF_UV_INVERSE_LAYERS;
-static_assert(NL == 3 + kUvInvHiddenLayers && kUvInvHiddenLayers == 2, "linear1, linear2, two hidden layers, last_linear");
 static_assert(NGF_UV_INVERSE_TRAIN_PARAMS == 2 * NL, "weight and bias of every layer");
-unsigned blocks(int64_t n, int b = 256) { return (unsigned)std::max<int64_t>(1, (n + b - 1) / b); }
 }  // namespace
 
 struct ngf_uv_inverse_trainer {
     int device = -1;
     int num_cus = 256;
     ngf_uv_inverse_desc desc{};
-    int out_f[NL], in_f[NL];
+    UvInvShape shape{};
     int64_t cap = 0;
     DeviceAllocs mem{0, 16};                 // every device buffer of the handle
     float *w = nullptr;                      // the packed sets
@@ -38,43 +36,6 @@ struct ngf_uv_inverse_trainer {
 
 namespace {
 
-// the segment table of uvit_pack_kernel.  The forward set comes first, in the order and at the offsets of ngf_uv_inverse.hip's InvPacker (every
-// image is a multiple of four floats, so its align() never pads); the transposed set follows.
-void plan_pack(ngf_uv_inverse_trainer *t, int64_t *total)
-{
-    const int D = t->desc.input_dim, M = kUvInvMid, H = kUvInvHidden;
-    int off = 0, ns = 0;
-    auto seg = [&](const float *src, int kind, int out_f, int in_f, int so, int si, int KT, int NT, int hid) {
-        UvitSeg &s = t->pack.seg[ns++];
-        s.src = src; s.dst = off; s.kind = kind; s.out_f = out_f; s.in_f = in_f; s.so = so; s.si = si; s.NT = NT; s.hid = hid;
-        s.count = kind == kUvitDense ? KT * NT * 64 : (kind == kUvitOut ? KT * 64 : (kind == kUvitBias ? NT * 16 : 4));
-        off += s.count;
-        return s.dst;
-    };
-    const float *const *w = t->desc.w, *const *b = t->desc.b;
-    UvInverseArgs &A = t->fwd;
-    A.dim = D;
-    A.w1 = seg(w[0], kUvitDense, M, D, D, 1, 4, M / 16, 0);      A.b1 = seg(b[0], kUvitBias, M, 0, 0, 0, 0, M / 16, 0);
-    A.w2 = seg(w[1], kUvitDense, H, M, M, 1, M / 4, H / 16, 1);  A.b2 = seg(b[1], kUvitBias, H, 0, 0, 0, 0, H / 16, 0);
-    A.wh = seg(w[2], kUvitDense, H, H, H, 1, H / 4, H / 16, 1);
-    (void)seg(w[3], kUvitDense, H, H, H, 1, H / 4, H / 16, 1);
-    A.bh = seg(b[2], kUvitBias, H, 0, 0, 0, 0, H / 16, 0);
-    (void)seg(b[3], kUvitBias, H, 0, 0, 0, 0, H / 16, 0);
-    A.wo = seg(w[4], kUvitOut, 3, H, H, 1, H / 4, 0, 1);         A.bo = seg(b[4], kUvitBias4, 3, 0, 0, 0, 0, 0, 0);
-    // the dX chain's layers: element (o, i) of layer^T is W[i, o]
-    UvitDxArgs &X = t->dx;
-    X.dim = D;
-    X.to = seg(w[4], kUvitDense, H, 3, 1, H, 4, H / 16, 0);              // d_xyz in natural order, as linear1 takes uv
-    X.th = seg(w[3], kUvitDense, H, H, 1, H, H / 4, H / 16, 1);
-    (void)seg(w[2], kUvitDense, H, H, 1, H, H / 4, H / 16, 1);
-    X.t2 = seg(w[1], kUvitDense, M, H, 1, M, H / 4, M / 16, 1);
-    X.t1 = seg(w[0], kUvitOut, D, M, 1, D, M / 4, 0, 1);
-    t->pack.nseg = ns;
-    X.zb = off;                                                          // zeros: the chain's bias in accumulator order (and its bias4)
-    off += (H / 16) * 16;
-    *total = off;
-}
-
 int pack_weights(ngf_uv_inverse_trainer *t, hipStream_t st)
 {
     int most = 0;
@@ -90,7 +51,7 @@ int weight_grads(ngf_uv_inverse_trainer *t, int l, const float *dz, int64_t ld_d
     UvitDw G{};
     G.dz = dz; G.ld_dz = ld_dz; G.x = x; G.ld_x = ld_x;
     G.part = t->part; G.partb = t->partb;
-    G.rows = t->n; G.M = t->out_f[l]; G.N = t->in_f[l];
+    G.rows = t->n; G.M = t->shape.out_f[l]; G.N = t->shape.in_f[l];
     G.chunk = (int32_t)uvit_chunk(t->n);
     const int nz = (int)((t->n + G.chunk - 1) / G.chunk);
     const dim3 grid(blocks(G.M, kUvitTile), blocks(G.N, kUvitTile), (unsigned)nz);
@@ -103,12 +64,6 @@ int weight_grads(ngf_uv_inverse_trainer *t, int l, const float *dz, int64_t ld_d
     NGF_LAUNCH(uvit_reduce_kernel, dim3(blocks(std::max<int64_t>(nk, G.M))), dim3(256), 0, st, (const float *)t->part, (const double *)t->partb, nk, G.M, nz,
                t->grads + t->grad_off[2 * l], t->grads + t->grad_off[2 * l + 1]);
     return NGF_OK;
-}
-
-int64_t tile_grid(const ngf_uv_inverse_trainer *t, int64_t n)
-{
-    const int64_t grid = ((n + kUvInvTilePoints - 1) / kUvInvTilePoints + kUvInvWaves - 1) / kUvInvWaves;
-    return std::min<int64_t>(grid, t->num_cus);
 }
 
 }  // namespace
@@ -132,10 +87,7 @@ int ngf_uv_inverse_trainer_create(const ngf_uv_inverse_desc *d, int64_t max_poin
 {
     if (!d || !out) return fail(NGF_E_ARG, "ngf_uv_inverse_trainer_create: null argument");
     *out = nullptr;
-    if (d->input_dim != 2 && d->input_dim != 3)
-        return fail(NGF_E_ARG, "ngf_uv_inverse_trainer_create: input_dim must be 2 (square) or 3 (sphere), got %d", d->input_dim);
-    for (int l = 0; l < NL; ++l)
-        if (!d->w[l] || !d->b[l]) return fail(NGF_E_ARG, "ngf_uv_inverse_trainer_create: layer %d missing", l);
+    if (int rc = check_inverse_desc("ngf_uv_inverse_trainer_create", d)) return rc;
     if (max_points <= 0 || max_points >= (int64_t)1 << 27)
         return fail(NGF_E_ARG, "ngf_uv_inverse_trainer_create: max_points must be in 1 .. 2^27 - 1, got %lld", (long long)max_points);
     hipStream_t st = (hipStream_t)hip_stream;
@@ -148,18 +100,24 @@ int ngf_uv_inverse_trainer_create(const ngf_uv_inverse_desc *d, int64_t max_poin
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess) t->num_cus = prop.multiProcessorCount;
     t->desc = *d;
     t->cap = max_points;
-    const int D = d->input_dim, M = kUvInvMid, H = kUvInvHidden;
-    const int kOut[NL] = {M, H, H, H, 3}, kIn[NL] = {D, M, H, H, H};
+    const int D = d->input_dim, H = kUvInvHidden;
+    t->shape = uv_inverse_shape(D);
+    const int *kOut = t->shape.out_f, *kIn = t->shape.in_f;
     int64_t g = 0;
     for (int l = 0; l < NL; ++l) {
-        t->out_f[l] = kOut[l]; t->in_f[l] = kIn[l];
         t->grad_off[2 * l] = g; g += (int64_t)kOut[l] * kIn[l];
         t->grad_off[2 * l + 1] = g; g += kOut[l];
         g = (g + 3) & ~(int64_t)3;
     }
     t->grad_elems = g;
-    int64_t wfloats = 0;
-    plan_pack(t, &wfloats);
+    // the packed sets: uvit_pack_kernel's segments read the caller's tensors where they are
+    const UvInvPlan P = uv_inverse_plan(D, d->w, d->b);
+    const int64_t wfloats = P.floats;
+    t->pack.nseg = P.nseg;
+    std::copy(P.seg, P.seg + P.nseg, t->pack.seg);
+    t->fwd.dim = t->dx.dim = D;
+    t->fwd.at = P.fwd;
+    t->dx.at = P.dx;
     // chunks of any batch the handle takes: uvit_chunk(n) >= 1024 rows, and at most 64 of them
     const int64_t nzmax = std::min<int64_t>(kUvitMaxChunks, (max_points + kUvitMinChunk - 1) / kUvitMinChunk);
     int rc = NGF_OK;
@@ -210,10 +168,7 @@ int ngf_uv_inverse_train_forward(ngf_uv_inverse_trainer *t, const float *uv, int
         A.q = t->fwd;
         A.q.uv = uv; A.q.xyz = xyz; A.q.n = n;
         for (int l = 0; l < NL - 1; ++l) A.keep[l] = t->keep[l];
-        if (int rc = poison_lds(st)) return rc;
-        const size_t lds = (size_t)kUvInvWaves * kUvInvWaveLds * sizeof(float);
-        HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(uvit_forward_kernel), lds));
-        NGF_LAUNCH(uvit_forward_kernel, dim3((unsigned)tile_grid(t, n)), dim3(64 * kUvInvWaves), lds, st, A);
+        if (int rc = launch_inverse_tiles(uvit_forward_kernel, A, n, t->num_cus, st)) return rc;
     }
     t->n = n;
     t->ticket = ++t->next_ticket;
@@ -241,14 +196,11 @@ int backward(ngf_uv_inverse_trainer *t, const char *who, int64_t ticket, const f
     }
     UvitDxArgs Q = t->dx;
     Q.d_xyz = d_xyz; Q.d_uv = d_uv; Q.n = n;
-    if (int rc = poison_lds(st)) return rc;
-    const size_t lds = (size_t)kUvInvWaves * kUvInvWaveLds * sizeof(float);
-    HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(uvit_dx_kernel), lds));
-    NGF_LAUNCH(uvit_dx_kernel, dim3((unsigned)tile_grid(t, n)), dim3(64 * kUvInvWaves), lds, st, Q);
+    if (int rc = launch_inverse_tiles(uvit_dx_kernel, Q, n, t->num_cus, st)) return rc;
     if (!with_dw) return NGF_OK;
     const int D = t->desc.input_dim;
     int rc = weight_grads(t, 4, d_xyz, 3, t->keep[3], kUvInvHidden, st);
-    for (int l = 3; l >= 1 && !rc; --l) rc = weight_grads(t, l, t->dz[l], t->out_f[l], t->keep[l - 1], t->out_f[l - 1], st);
+    for (int l = 3; l >= 1 && !rc; --l) rc = weight_grads(t, l, t->dz[l], t->shape.out_f[l], t->keep[l - 1], t->shape.out_f[l - 1], st);
     if (!rc) rc = weight_grads(t, 0, t->dz[0], kUvInvMid, t->uv, D, st);
     if (rc) return rc;
     t->have_grads = true;
@@ -278,7 +230,7 @@ int ngf_uv_inverse_train_get_grads(ngf_uv_inverse_trainer *t, float *const out[N
     for (int k = 0; k < NGF_UV_INVERSE_TRAIN_PARAMS; ++k) {
         if (!out[k]) continue;
         const int l = k / 2;
-        const int64_t n = (k & 1) ? t->out_f[l] : (int64_t)t->out_f[l] * t->in_f[l];
+        const int64_t n = (k & 1) ? t->shape.out_f[l] : (int64_t)t->shape.out_f[l] * t->shape.in_f[l];
         HIP_TRY(hipMemcpyAsync(out[k], t->grads + t->grad_off[k], (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return NGF_OK;

@@ -1,12 +1,12 @@
 // ngf_uv_inverse_train.hpp -- NeuTex's inverse gauge (ngf_uv_inverse.hpp: uv [n, D] -> 64 -> 512 -> 512 -> 512 -> xyz, ReLU) with a backward
 // pass; host side in ngf_uv_inverse_train.hip, DESIGN.md section 4.13.
 //
-//   uvit_pack_kernel     gathers the caller's ten tensors into the streamed layouts of ngf_uv.hpp's blocks ON THE DEVICE: the forward set (bit for
-//                        bit the host InvPacker's of ngf_uv_inverse.hip) and the transposed set the dX chain reads.  The weights change every
-//                        optimiser step; a host round trip per step would cost more than the network.
-//   uvit_forward_kernel  uv_inverse_kernel's arithmetic -- same blocks, same order, one 16-point tile per wave, four waves and 128 KB of LDS per
-//                        CU, hence the same bits -- which also keeps the POST-activation outputs of the four hidden layers (their sign is the
-//                        derivative torch uses: relu(z) > 0 iff z > 0; and they are the dW products' right operands as they are).
+//   uvit_pack_kernel     gathers the caller's ten tensors into the streamed layouts of ngf_uv.hpp's blocks ON THE DEVICE: the forward set (the
+//                        segments ngf_uv_inverse_create packs on the host, through the same ngf_uv_pack.hpp) and the transposed set the dX
+//                        chain reads.  The weights change every optimiser step; a host round trip per step would cost more than the network.
+//   uvit_forward_kernel  uv_inverse_kernel's pass (ngf_uv_inverse.hpp: uv_inverse_pass, the one text of both) -- hence the same bits -- which
+//                        also keeps the POST-activation outputs of the four hidden layers (their sign is the derivative torch uses:
+//                        relu(z) > 0 iff z > 0; and they are the dW products' right operands as they are).
 //   uvit_dx_kernel       the forward mirrored: d_xyz (padded to four k-steps, as linear1 pads uv) -> 512 -> 512 -> 512 -> 64 -> D through dense /
 //                        kstep / store_act / dense_out with ACT = kUvActNone, the transposed weights and a zero bias.  Each layer's accumulators
 //                        are masked by the kept outputs before they are stored; every layer's dZ also goes to memory for the weight gradients.
@@ -21,7 +21,6 @@
 // A tail tile's padding lanes evaluate the last point again (as in the forward) and neither store kept outputs nor dZ: the dW products run over
 // rows 0..n-1 only, so they contribute nothing.
 #pragma once
-#define NGF_UV_INVERSE_NO_KERNEL
 #include "ngf_uv_inverse.hpp"
 
 namespace ngf {
@@ -37,51 +36,17 @@ __host__ __device__ inline int64_t uvit_chunk(int64_t n)
 }
 
 // ---- device packer -----------------------------------------------------------------------------------------------------------------------
-// One segment = one packed layer image; element (o, i) of the layer it packs is src[o so + i si] (so = in, si = 1: W as stored; so = 1, si = the
-// stored row length: its transpose).
-enum { kUvitDense = 0, kUvitOut = 1, kUvitBias = 2, kUvitBias4 = 3 };
-struct UvitSeg {
-    const float *src;
-    int32_t dst, count;      // floats
-    int32_t kind;
-    int32_t out_f, in_f, so, si;
-    int32_t NT;              // unit tiles (dense: [KT][NT / 4][64][4]; bias: [4][NT][4])
-    int32_t hid;             // input order: 0 natural (4 t + kq), 1 the producing layer's accumulator order
-    int32_t pad_;
-};
-constexpr int kUvitSegs = 16;
+// Every segment of the plan (ngf_uv_pack.hpp: uv_inverse_plan), one grid row each; what a word holds is uv_pack_value's to say.
 struct UvitPack {
     float *dst;
     int32_t nseg, pad_;
-    UvitSeg seg[kUvitSegs];
+    UvPackSeg seg[kUvInvSegs];
 };
 
 __global__ void __launch_bounds__(256) uvit_pack_kernel(const UvitPack P)
 {
-    const UvitSeg &S = P.seg[blockIdx.y];
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < S.count; idx += gridDim.x * 256) {
-        float v = 0.0f;
-        if (S.kind == kUvitDense || S.kind == kUvitOut) {
-            const int e = idx & 3, l = (idx >> 2) & 63, rest = idx >> 8, kq = l >> 4;
-            int t, o;
-            if (S.kind == kUvitDense) {
-                const int g = rest % (S.NT / 4);
-                t = rest / (S.NT / 4);
-                o = (4 * g + e) * 16 + (l & 15);
-            } else {
-                t = 4 * rest + e;
-                o = l & 15;
-            }
-            const int i = S.hid ? (t >> 2) * 16 + 4 * kq + (t & 3) : 4 * t + kq;
-            if (o < S.out_f && i < S.in_f) v = S.src[(int64_t)o * S.so + (int64_t)i * S.si];
-        } else if (S.kind == kUvitBias) {
-            const int r = idx & 3, mt = (idx >> 2) % S.NT, kq = idx / (4 * S.NT);
-            v = S.src[mt * 16 + 4 * kq + r];
-        } else {
-            if (idx < S.out_f) v = S.src[idx];
-        }
-        P.dst[S.dst + idx] = v;
-    }
+    const UvPackSeg &S = P.seg[blockIdx.y];
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < S.count; idx += gridDim.x * 256) P.dst[S.dst + idx] = uv_pack_value(S, idx);
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------------
@@ -90,71 +55,7 @@ struct UvitFwdArgs {
     float *keep[2 + kUvInvHiddenLayers];      // relu(outputs) of linear1 [n, 64], linear2 and the hidden layers [n, 512]
 };
 
-// relu(acc) of a live lane's point to its row-major row (row: the point's row + 4 kq)
-template <int NT>
-__device__ __forceinline__ void uvit_keep(float *row, bool live, const f32x4 acc[1][NT])
-{
-    if (live) {
-#pragma unroll
-        for (int mt = 0; mt < NT; ++mt) {
-            f32x4 v;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = act_fn<0>(acc[0][mt][r]);
-            *reinterpret_cast<f32x4 *>(row + mt * 16) = v;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(64 * kUvInvWaves) uvit_forward_kernel(const UvitFwdArgs A)
-{
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const UvInverseArgs &Q = A.q;
-    int lane = threadIdx.x & 63;
-    float *act = smem + (threadIdx.x >> 6) * kUvInvWaveLds;
-    const int64_t passes = (Q.n + kUvInvTilePoints - 1) / kUvInvTilePoints, stride = (int64_t)gridDim.x * kUvInvWaves;
-    for (int64_t p = (int64_t)blockIdx.x * kUvInvWaves + (threadIdx.x >> 6); p < passes; p += stride) {
-        // (uv_inverse_kernel's pass, statement for statement; the uvit_keep calls are the additions)
-        int wz = 0;
-        asm volatile("" : "+s"(wz), "+v"(lane));
-        const float *W = Q.w + wz;
-        const int kq = lane >> 4;
-        const int64_t idx = p * kUvInvTilePoints + (lane & 15);
-        const bool live = idx < Q.n;
-        const int64_t i = live ? idx : Q.n - 1;
-        const int kc = kq < Q.dim ? kq : Q.dim - 1;
-        const float xc = Q.uv[i * Q.dim + kc];
-        const float x = kq < Q.dim ? xc : 0.0f;
-        KStepA<32, 1> pre[4];
-        uv_wprefetch<32, 1>(W + Q.w2, lane, pre);
-        act[lane] = x;
-#pragma unroll
-        for (int t = 1; t < 4; ++t) act[t * 64 + lane] = 0.0f;
-        f32x4 h4[1][4], h[1][32];
-        dense<4, 1, true>(W + Q.w1, W + Q.b1, 4, lane, act, h4);
-        store_act<4, 1, kUvActNone>(act, lane, h4);
-        uvit_keep<4>(A.keep[0] + idx * kUvInvMid + 4 * kq, live, h4);
-        dense<32, 1, true, 0>(W + Q.w2, W + Q.b2, kUvInvMid / 4, lane, act, h, 1 << 30, pre, true);
-#pragma unroll 1
-        for (int l = 0; l < kUvInvHiddenLayers; ++l) {
-            const float *wl = W + Q.wh + (size_t)l * (kUvInvHidden * kUvInvHidden);
-            uv_wprefetch<32, 1>(wl, lane, pre);
-            store_act<32, 1, kUvActNone>(act, lane, h);
-            uvit_keep<32>(A.keep[1 + l] + idx * kUvInvHidden + 4 * kq, live, h);
-            dense<32, 1, true, 0>(wl, W + Q.bh + l * kUvInvHidden, kUvInvRows, lane, act, h, 1 << 30, pre, true);
-        }
-        UvOutW<kUvInvRows> ow;
-        store_act<32, 1, kUvActNone>(act, lane, h);
-        out_prefetch<kUvInvRows>(W + Q.wo, lane, ow);
-        uvit_keep<32>(A.keep[1 + kUvInvHiddenLayers] + idx * kUvInvHidden + 4 * kq, live, h);
-        __builtin_amdgcn_sched_barrier(0);
-        f32x4 o[1];
-        dense_out<1, kUvInvRows, 0, true>(ow, W + Q.bo, lane, act, o);
-        if (lane < 16 && live) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) Q.xyz[idx * 3 + k] = o[0][k];
-        }
-    }
-}
+__global__ void __launch_bounds__(64 * kUvInvWaves) uvit_forward_kernel(const UvitFwdArgs A) { uv_inverse_pass<true>(A.q, A.keep); }
 
 // ---- dX chain --------------------------------------------------------------------------------------------------------------------------------
 struct UvitDxArgs {
@@ -165,7 +66,7 @@ struct UvitDxArgs {
     float *dz[2 + kUvInvHiddenLayers];               // d loss / d pre-activation of the same layers
     int64_t n;
     int32_t dim;
-    int32_t to, th, t2, t1, zb;      // last_linear^T (3 -> 512), the hidden layers^T LAST FIRST (stride 512 * 512), linear2^T (512 -> 64), linear1^T (64 -> D, output layout), zeros
+    UvInvDxAt at;
 };
 
 // acc <- acc where the kept output is positive, else 0 (torch's threshold_backward); a live lane's result to its dZ row.  The sched_barrier keeps
@@ -205,29 +106,29 @@ __global__ void __launch_bounds__(64 * kUvInvWaves) uvit_dx_kernel(const UvitDxA
         for (int t = 1; t < 4; ++t) act[t * 64 + lane] = 0.0f;
         f32x4 h4[1][4], h[1][32];
         KStepA<32, 1> pre[4];
-        dense<32, 1, true>(W + Q.to, W + Q.zb, 4, lane, act, h);
+        dense<32, 1, true>(W + Q.at.to, W + Q.at.zb, 4, lane, act, h);
         uvit_mask_store<32>(Q.keep[1 + kUvInvHiddenLayers] + i * kUvInvHidden + 4 * kq, Q.dz[1 + kUvInvHiddenLayers] + idx * kUvInvHidden + 4 * kq, live, h);
 #pragma unroll 1
         for (int l = 0; l < kUvInvHiddenLayers; ++l) {
-            const float *wl = W + Q.th + (size_t)l * (kUvInvHidden * kUvInvHidden);
+            const float *wl = W + Q.at.th + (size_t)l * (kUvInvHidden * kUvInvHidden);
             uv_wprefetch<32, 1>(wl, lane, pre);
             store_act<32, 1, kUvActNone>(act, lane, h);
-            dense<32, 1, true>(wl, W + Q.zb, kUvInvRows, lane, act, h, 1 << 30, pre, true);
+            dense<32, 1, true>(wl, W + Q.at.zb, kUvInvRows, lane, act, h, 1 << 30, pre, true);
             const int k = kUvInvHiddenLayers - l;        // the layer whose pre-activation gradient this is: 2, 1
             uvit_mask_store<32>(Q.keep[k] + i * kUvInvHidden + 4 * kq, Q.dz[k] + idx * kUvInvHidden + 4 * kq, live, h);
         }
         KStepA<4, 1> pre4[4];
-        uv_wprefetch<4, 1>(W + Q.t2, lane, pre4);
+        uv_wprefetch<4, 1>(W + Q.at.t2, lane, pre4);
         store_act<32, 1, kUvActNone>(act, lane, h);
-        dense<4, 1, true>(W + Q.t2, W + Q.zb, kUvInvRows, lane, act, h4, 1 << 30, pre4, true);
+        dense<4, 1, true>(W + Q.at.t2, W + Q.at.zb, kUvInvRows, lane, act, h4, 1 << 30, pre4, true);
         uvit_mask_store<4>(Q.keep[0] + i * kUvInvMid + 4 * kq, Q.dz[0] + idx * kUvInvMid + 4 * kq, live, h4);
         if (Q.d_uv) {          // (uniform)
             UvOutW<kUvInvMid / 4> ow;
             store_act<4, 1, kUvActNone>(act, lane, h4);
-            out_prefetch<kUvInvMid / 4>(W + Q.t1, lane, ow);
+            out_prefetch<kUvInvMid / 4>(W + Q.at.t1, lane, ow);
             __builtin_amdgcn_sched_barrier(0);
             f32x4 o[1];
-            dense_out<1, kUvInvMid / 4, kUvActNone>(ow, W + Q.zb, lane, act, o);
+            dense_out<1, kUvInvMid / 4, kUvActNone>(ow, W + Q.at.zb, lane, act, o);
             // the four lanes of a point hold the same values: quarter 0 stores them, plain stores
             if (lane < 16 && live) {
                 for (int k = 0; k < Q.dim; ++k) Q.d_uv[idx * Q.dim + k] = k == 0 ? o[0][0] : (k == 1 ? o[0][1] : o[0][2]);

@@ -33,8 +33,6 @@ void layer_shapes(int sphere, LayerShape s[L])
     s[i++] = {256, 3, kNone};
 }
 
-unsigned blocks(int64_t n, int b = 256) { return (unsigned)std::max<int64_t>(1, (n + b - 1) / b); }
-
 }  // namespace
 
 struct ngf_uv_trainer {

@@ -34,12 +34,8 @@ def _bind(L):
 
 
 def inverse_params(gauge):
-    """The ten tensors in the trainer's slot order: weight, bias of linear1, linear2, linear_list.{0,1}, last_linear (NeuTex.inverse_layers())."""
-    n = gauge.inverse_network
-    out = []
-    for lin in [n.linear1, n.linear2, n.linear_list[0], n.linear_list[1], n.last_linear]:
-        out += [lin.weight, lin.bias]
-    return out
+    """The ten tensors in the trainer's slot order: weight, bias of each of ``gauge.layers()``."""
+    return [t for lin in gauge.layers() for t in (lin.weight, lin.bias)]
 
 
 class InverseGrad(GradEngine):
@@ -63,10 +59,7 @@ class InverseGrad(GradEngine):
         _bind(self.L)
         self.dim = int(gauge.input_point_dim)
         self.forwards = 0               # launches of the training forward (a stale ticket shows as one more than the calls made)
-        d = _lib.UvInverseDesc()
-        d.input_dim = self.dim
-        for i in range(_lib.UV_INVERSE_LAYERS):
-            d.w[i], d.b[i] = params[2 * i].data_ptr(), params[2 * i + 1].data_ptr()
+        d = _lib.uv_inverse_desc(self.dim, params)
         out = C.c_void_p()
         with on_stream(dev) as st:
             _lib.check(self.L.ngf_uv_inverse_trainer_create(C.byref(d), self.max_rays, C.byref(out), st))

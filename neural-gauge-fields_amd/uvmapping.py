@@ -221,6 +221,12 @@ class InverseGauge(nn.Module):
         self.num_points_per_primitive = int(num_points_per_primitive)
         self.inverse_network = InverseNetwork(self.input_point_dim)
 
+    def layers(self):
+        """The five Linear layers of the inverse network in the order of ngf_uv_inverse_desc (the one list: NeuTex.inverse_layers() and
+        uv_inverse_train.inverse_params() are built on it)."""
+        n = self.inverse_network
+        return [n.linear1, n.linear2, n.linear_list[0], n.linear_list[1], n.last_linear]
+
     def random_points(self, n):
         dev = self.inverse_network.linear1.weight.device
         with torch.no_grad():
@@ -518,8 +524,7 @@ class NeuTex(nn.Module):
     # --- the inverse gauge on the GPU (include/ngf.h: ngf_uv_inverse_map) -------------------------------------------
     def inverse_layers(self):
         """The five Linear layers of the inverse network in the order of ngf_uv_inverse_desc."""
-        n = self.inverse_gauge.inverse_network
-        return [n.linear1, n.linear2, n.linear_list[0], n.linear_list[1], n.last_linear]
+        return self.inverse_gauge.layers()
 
     def inverse_handle(self):
         """The packed inverse network (ngf_uv_inverse), rebuilt when a parameter of it was written in place or replaced -- ``handle()``'s key."""
@@ -527,14 +532,8 @@ class NeuTex(nn.Module):
         if self._inv_handle is not None and key == self._inv_key:
             return self._inv_handle
         dev = self._gpu("runs the inverse gauge")
-        d = _lib.UvInverseDesc()
-        d.input_dim = self.inverse_gauge.input_point_dim
-        keep = []
-        for i, lin in enumerate(self.inverse_layers()):
-            w = lin.weight.detach().to(dev, torch.float32).contiguous()
-            b = lin.bias.detach().to(dev, torch.float32).contiguous()
-            keep += [w, b]
-            d.w[i], d.b[i] = w.data_ptr(), b.data_ptr()
+        keep = [t.detach().to(dev, torch.float32).contiguous() for lin in self.inverse_layers() for t in (lin.weight, lin.bias)]
+        d = _lib.uv_inverse_desc(self.inverse_gauge.input_point_dim, keep)
         out = C.c_void_p()
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().ngf_uv_inverse_create(C.byref(d), C.byref(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)))

@@ -84,14 +84,14 @@ def _links_and_runs(cxx, flags, workdir):
     return subprocess.run([exe], capture_output=True).returncode == 0
 
 
-def compile_program(workdir, flags=None):
-    """Compiles the program into workdir; returns (path, flags used).  flags = None: the sanitizer build, or -- only where a one-line probe with
-    those flags does not link and run on this machine -- the same without sanitizers."""
+def compile_program(workdir, flags=None, source=SOURCE):
+    """Compiles the stand-alone program ``source`` (tests/host/*.cpp) into workdir; returns (path, flags used).  flags = None: the sanitizer
+    build, or -- only where a one-line probe with those flags does not link and run on this machine -- the same without sanitizers."""
     cxx = compiler()
     if flags is None:
         flags = SANITIZE if _links_and_runs(cxx, SANITIZE, workdir) else ["-O1", "-g"]
-    exe = os.path.join(workdir, "mlp_image_main")
-    subprocess.run([cxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", *flags, "-I", CSRC, SOURCE, "-o", exe], check=True)
+    exe = os.path.join(workdir, os.path.splitext(os.path.basename(source))[0])
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", *flags, "-I", CSRC, source, "-o", exe], check=True)
     return exe, flags
 
 
