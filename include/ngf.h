@@ -494,6 +494,37 @@ int ngf_uv_query(const ngf_uv *m, const float *xyz, int64_t n, const float *view
                  float *sigma /*[n] or NULL*/, float *uv /*[n,3] or NULL; z = 0 for square*/, float *rgb /*[n,3] or NULL*/, void *hip_stream);
 int ngf_uv_density_lattice(const ngf_uv *m, const float lo[3], const float step[3], int32_t nx, int32_t ny, int32_t nz, int32_t flags,
                            float *sigma /*[nx,ny,nz]*/, void *hip_stream);
+/* Occupancy grid (additive, ABI 5): the render of a handle skips empty space.  OPT-IN: the masked frame is, by definition, the reference's frame
+ * with sigma set to 0 in empty cells -- not the reference's frame.
+ *   Grid     nx x ny x nz cells over the cube [-1,1]^3, one bit per cell (1 = occupied); cell (cx,cy,cz) has linear index (cx ny + cy) nz + cz, the
+ *            C order of ngf_uv_density_lattice; bits packed like np.packbits (most significant bit first, as ngf_pack_mask_bits packs) into
+ *            (nx ny nz + 7) / 8 bytes, the tail bits of the last byte 0.
+ *   Look-up  of a float32 point p: c_k = min(int(floorf((p_k + 1.0f) * h_k)), n_k - 1) with h_k = (float)n_k * 0.5f, the add and the multiply each
+ *            rounded (for p_k = 1 - 2^-24 the sum rounds to 2.0: hence the clamp).  A point that fails the render's strict in-cube test
+ *            -1 < p_k < 1 (NaN fails it) is not occupied, and only points that pass it load a byte.
+ *   Render   with a mask installed (ngf_uv_set_occupancy) a sample is valid iff in-cube AND occupied(p).  A sample that is not valid contributes
+ *            what an out-of-cube sample does: opacity 0, colour 0; it is not evaluated and dbg_sigma / dbg_col hold 0 for it.  An evaluated
+ *            sample's sigma and colour are the same bits as without a mask.  ngf_uv_render / ngf_uv_render_batch keep their signatures; their
+ *            `stats` then count the samples actually evaluated and the passes actually run.  The one-ray-per-wave experiment knob (uv_tiles = 1)
+ *            with a mask installed returns NGF_E_ARG.  Without a mask every launch runs the kernels it ran before.
+ * ngf_uv_occupancy_from_lattice: sigma = float32 [(nx+1),(ny+1),(nz+1)] (C order, DEVICE) -- ngf_uv_density_lattice with lo = -1, step_k =
+ *   float32(2 / n_k) and NGF_UV_QUERY_NO_CLIP (with the clip the face corners read 0) -> bits (DEVICE, (nx ny nz + 7) / 8 bytes).  m(cell) = the max
+ *   of the cell's 8 corners; a cell is HOT iff !(m <= threshold), so a NaN corner makes it hot; a cell is OCCUPIED iff some cell within Chebyshev
+ *   distance `dilate` (0, 1 or 2) of it, inside the grid, is hot.  workspace: DEVICE, at least ngf_uv_occupancy_workspace_bytes(nx, ny, nz) bytes
+ *   (that call returns -NGF_E_ARG for an axis outside 1 .. 1024).  No atomics; every output byte is written once, whole, by one thread; nothing is
+ *   written past the image; the output is a function of the inputs alone.  Asynchronous on the stream.
+ * ngf_uv_set_occupancy: copies the bits (DEVICE) into the handle, like ngf_uv_set_texture; bits_dev = NULL switches the mask off.  It waits for
+ *   the device when it replaces or drops a mask.
+ * ngf_uv_occupancy_lookup: out[i] = 1 if xyz[i] (DEVICE [n,3]) is occupied in the handle's mask, else 0 -- the render's own look-up function.
+ * NGF_E_ARG, before any GPU work: null pointers, an axis outside 1 .. 1024, dilate outside 0 .. 2, a NaN threshold, a workspace that is too small,
+ * n < 0, a look-up on a handle without a mask.  n == 0 returns NGF_OK without a launch.
+ * The mask is the RENDER's alone: ngf_uv_query, ngf_uv_density_lattice, the texture calls (ngf_uv_texture_eval, ngf_uv_texture_edit) and the
+ * trainer (ngf_uv_train_*) do not consult it. */
+int64_t ngf_uv_occupancy_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int ngf_uv_occupancy_from_lattice(const float *sigma, int32_t nx, int32_t ny, int32_t nz, float threshold, int32_t dilate, uint8_t *bits,
+                                  void *workspace, int64_t workspace_bytes, void *hip_stream);
+int ngf_uv_set_occupancy(ngf_uv *m, const uint8_t *bits_dev, int32_t nx, int32_t ny, int32_t nz, void *hip_stream);
+int ngf_uv_occupancy_lookup(const ngf_uv *m, const float *xyz, int64_t n, uint8_t *out, void *hip_stream);
 /* The inverse gauge: NeuTex's fourth network, inverse_gauge.inverse_network (gauge_fields.py:78-120, a modified AtlasNet core), which takes a
  * point of the atlas template (uv in R^2 for square models, a direction in R^3 for sphere models) back to the world.  A handle of its own:
  * five nn.Linear layers in evaluation order, reference layouts (weight [out,in], bias [out], float32, device):

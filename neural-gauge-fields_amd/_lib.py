@@ -34,6 +34,7 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_debug_ii_product", "ngf_debug_ii_counts",
            "ngf_mesh_workspace_bytes", "ngf_mesh_count", "ngf_mesh_emit", "ngf_debug_mesh_scan",
            "ngf_field_query", "ngf_uv_query", "ngf_uv_density_lattice",
+           "ngf_uv_occupancy_workspace_bytes", "ngf_uv_occupancy_from_lattice", "ngf_uv_set_occupancy", "ngf_uv_occupancy_lookup",
            "ngf_uv_inverse_create", "ngf_uv_inverse_destroy", "ngf_uv_inverse_map",
            "ngf_uv_inverse_trainer_create", "ngf_uv_inverse_trainer_destroy", "ngf_uv_inverse_trainer_bytes", "ngf_uv_inverse_train_params_changed",
            "ngf_uv_inverse_train_forward", "ngf_uv_inverse_train_backward", "ngf_uv_inverse_train_get_grads", "ngf_debug_uv_inverse_train_dx"]
@@ -142,6 +143,12 @@ def _load(path):
         L.ngf_uv_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ngf_uv_density_lattice.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_void_p]
+        L.ngf_uv_occupancy_workspace_bytes.restype = C.c_int64
+        L.ngf_uv_occupancy_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        L.ngf_uv_occupancy_from_lattice.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                                    C.c_void_p]
+        L.ngf_uv_set_occupancy.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        L.ngf_uv_occupancy_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ngf_uv_inverse_create.argtypes = [C.POINTER(UvInverseDesc), C.POINTER(C.c_void_p), C.c_void_p]
         L.ngf_uv_inverse_destroy.argtypes = [C.c_void_p]
         L.ngf_uv_inverse_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]

@@ -10,6 +10,7 @@ using namespace ngf;
 struct ngf_uv {
     float *w = nullptr;
     float *tex = nullptr;          // owned copy of the edit texture (ngf_uv_set_texture)
+    uint8_t *occ = nullptr;        // owned copy of the occupancy bits (ngf_uv_set_occupancy)
     unsigned int *counters = nullptr;
     mutable std::atomic<unsigned> next_counter{0};
     UvArgs proto;
@@ -23,6 +24,7 @@ extern "C" int ngf_uv_destroy(ngf_uv *m)
     DeviceScope ds(m->dev);        // hipFree waits for the device's work: on the handle's device, whatever is current in the calling thread
     if (m->w) (void)hipFree(m->w);
     if (m->tex) (void)hipFree(m->tex);
+    if (m->occ) (void)hipFree(m->occ);
     if (m->counters) (void)hipFree(m->counters);
     delete m;
     return NGF_OK;
@@ -207,6 +209,33 @@ extern "C" int ngf_uv_set_texture(ngf_uv *m, const float *tex, int32_t faces, in
     return NGF_OK;
 }
 
+extern "C" int ngf_uv_set_occupancy(ngf_uv *m, const uint8_t *bits_dev, int32_t nx, int32_t ny, int32_t nz, void *hip_stream)
+{
+    if (!m) return fail(NGF_E_ARG, "ngf_uv_set_occupancy: null model");
+    if (bits_dev && (nx < 1 || ny < 1 || nz < 1 || nx > kUvOccMaxAxis || ny > kUvOccMaxAxis || nz > kUvOccMaxAxis))
+        return fail(NGF_E_ARG, "ngf_uv_set_occupancy: a grid of %d x %d x %d cells (every axis needs 1 .. %d)", nx, ny, nz, kUvOccMaxAxis);
+    DeviceScope ds(m->dev);
+    uint8_t *fresh = nullptr;
+    if (bits_dev) {
+        const size_t nbytes = ((size_t)nx * ny * nz + 7) / 8;
+        HIP_TRY(hipMalloc((void **)&fresh, nbytes));
+        if (hipMemcpyAsync(fresh, bits_dev, nbytes, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream) != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(NGF_E_HIP, "ngf_uv_set_occupancy: copying the bits failed");
+        }
+    }
+    if (m->occ) (void)hipFree(m->occ);          // (waits for the device's work: no launch still reads the old bits)
+    m->occ = fresh;
+    UvArgs &A = m->proto;
+    A.occ = fresh;
+    const int32_t n[3] = {nx, ny, nz};
+    for (int k = 0; k < 3; ++k) {
+        A.occ_n[k] = fresh ? n[k] : 0;
+        A.occ_h[k] = fresh ? (float)n[k] * 0.5f : 0.0f;
+    }
+    return NGF_OK;
+}
+
 extern "C" int ngf_uv_texture_edit(const ngf_uv *m, const float *uv, const float *orig, int64_t n, float *out, void *hip_stream)
 {
     if (!m || !uv || !orig || !out || n < 0) return fail(NGF_E_ARG, "ngf_uv_texture_edit: bad argument");
@@ -242,7 +271,15 @@ static int uv_launch(const ngf_uv *m, UvArgs &A, hipStream_t st)
     // two rays per wave (every weight load feeds two MFMAs, 4 waves per CU) unless ngf_debug_set("uv_tiles", 1) (one ray per wave, 8 waves)
     int tiles = 2;
     if (knob(KNOB_UV_TILES) >= 0) tiles = knob(KNOB_UV_TILES);
-    if (tiles == 2 && A.split_bf16) {
+    if (A.occ && tiles != 2) {
+        return fail(NGF_E_ARG, "a handle with an occupancy mask runs the two-rays-per-wave kernels only (knob uv_tiles must stay 2)");
+    } else if (A.occ && A.split_bf16) {
+        HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(uv_render_kernel<2, true, true>), lds));
+        hipLaunchKernelGGL((uv_render_kernel<2, true, true>), dim3((unsigned)grid), dim3(256), lds, st, A);
+    } else if (A.occ) {
+        HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(uv_render_kernel<2, false, true>), lds));
+        hipLaunchKernelGGL((uv_render_kernel<2, false, true>), dim3((unsigned)grid), dim3(256), lds, st, A);
+    } else if (tiles == 2 && A.split_bf16) {
         HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(uv_render_kernel<2, true>), lds));
         hipLaunchKernelGGL((uv_render_kernel<2, true>), dim3((unsigned)grid), dim3(256), lds, st, A);
     } else if (tiles == 2) {

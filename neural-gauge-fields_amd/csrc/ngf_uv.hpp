@@ -16,6 +16,7 @@
 // reference (sigma * valid, renderer.py:222), so skipping them changes nothing.
 #pragma once
 #include "ngf_device.hpp"
+#include "ngf_uv_occupancy.hpp"
 
 namespace ngf {
 
@@ -75,6 +76,11 @@ struct UvArgs {
     int32_t t1_w0, t1_b0, t1_wh, t1_bh, c1_w, c1_b, t2_w0, t2_b0, t2_wh, t2_bh, t2_wo, t2_bo;
     // split mode: bf16 images of the 256 -> 256 layers (stride kUvQLayer floats) and of block2.0 (10 k-blocks)
     int32_t geo_qh, t1_qh, t2_q0, t2_qh;
+    // occupancy grid (ngf_uv_set_occupancy; ngf_uv_occupancy.hpp), appended: the members above keep their offsets.  occ = NULL: none (the launch
+    // then runs the instantiations without the look-up); else the packed bits of occ_n[0] x occ_n[1] x occ_n[2] cells, occ_h[k] = (float)occ_n[k] * 0.5f
+    const uint8_t *occ;
+    int32_t occ_n[3];
+    float occ_h[3];
 };
 
 // Activations of the three MLPs.  ReLU (geometry, gauge: decoder.py:205-215, gauge_fields.py:20-33) as ONE integer maximum of the bit
@@ -1017,8 +1023,9 @@ __device__ __forceinline__ void uv_networks(const UvArgs &A, float *act, int lan
 
 // One wave renders NS rays at a time: lane i owns sample i of a 64-sample chunk of each (segment jitter, prefix sum, position,
 // in-cube test); the in-cube samples of the NS rays form ONE list (ray 0's first) that is pushed through the networks NS x 16 at
-// a time.
-template <int NS, bool SPLIT = false>
+// a time.  OCC: the handle has an occupancy grid and a sample is valid iff it is in the cube AND its cell's bit is set -- an unoccupied sample is what
+// an out-of-cube sample is: not evaluated, opacity 0, colour 0, zeros in the debug outputs.  The frame is the reference's with sigma = 0 in empty cells.
+template <int NS, bool SPLIT = false, bool OCC = false>
 __global__ void __launch_bounds__(512 / NS) uv_render_kernel(const UvArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1092,6 +1099,9 @@ __global__ void __launch_bounds__(512 / NS) uv_render_kernel(const UvArgs A)
                 for (int k = 0; k < 3; ++k) {
                     p[j][k] = cp[j][k] + d[j][k] * mid;
                     valid[j] = valid[j] && (p[j][k] > -1.0f) && (p[j][k] < 1.0f);
+                }
+                if constexpr (OCC) {
+                    if (valid[j]) valid[j] = uv_occ_lookup(A.occ, A.occ_n, A.occ_h, p[j]);          // (only in-cube lanes load a byte)
                 }
                 vm[j] = __ballot(valid[j]);
                 nv[j] = __popcll(vm[j]);

@@ -18,6 +18,11 @@ Point queries: ``NeuTex.query`` (density, gauge uv, colour at world points), ``N
 ``vt`` coordinates map the exported atlas onto the marching-cubes surface) run the three MLPs on explicit points in a HIP kernel of their own
 (include/ngf.h: ngf_uv_query, ngf_uv_density_lattice).
 
+Occupancy grid: ``NeuTex.build_occupancy`` reduces a density lattice to one bit per cell on the device and installs it; the render kernel then
+evaluates only the in-cube samples whose cell is occupied (include/ngf.h: ngf_uv_occupancy_from_lattice, ngf_uv_set_occupancy; DESIGN.md section
+4.14).  Opt-in: the masked frame is the reference's frame with sigma set to 0 in empty cells.  ``set_occupancy`` / ``occupancy`` / ``occupied`` /
+``occupancy_state`` / ``load_occupancy`` are the rest of the surface.
+
 Inverse gauge: ``NeuTex.inverse_map`` (template point -> world point), ``NeuTex.cycle_error`` and ``NeuTex.coordinate_deformation`` (the
 reference's deformed-template mesh, model.py:383-418) run ``inverse_gauge.inverse_network`` in a HIP kernel of its own (include/ngf.h:
 ngf_uv_inverse_map).  They build no graph.  With ``net.inverse_gauge.differentiable = True`` (an attribute, never saved),
@@ -306,6 +311,40 @@ def lattice_axes(resolution, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.0)):
     return res, lo32, step
 
 
+OCCUPANCY_MAX_AXIS, OCCUPANCY_MAX_DILATE = 1024, 2          # csrc/ngf_uv_occupancy.hpp: kUvOccMaxAxis, kUvOccMaxDilate
+
+
+def _occupancy_shape(shape):
+    """``shape`` as a triple of cell counts, each 1 .. 1024 (an int means a cube)."""
+    res = (int(shape),) * 3 if np.ndim(shape) == 0 else tuple(int(r) for r in shape)
+    if len(res) != 3 or min(res) < 1 or max(res) > OCCUPANCY_MAX_AXIS:
+        raise ValueError(f"an occupancy grid has three axes of 1 .. {OCCUPANCY_MAX_AXIS} cells, got {shape!r}")
+    return res
+
+
+class Occupancy:
+    """The occupancy grid of a NeuTex (``NeuTex.occupancy``): ``shape`` = (nx, ny, nz) cells over the cube [-1,1]^3, ``bits`` = the packed mask on
+    the model's device (uint8, ``np.packbits`` order over the C-ordered cells, tail bits 0), ``threshold`` / ``dilate`` = what ``build_occupancy``
+    built it with (None for a mask that was set or loaded)."""
+
+    def __init__(self, bits, shape, threshold=None, dilate=None):
+        self.bits, self.shape, self.threshold, self.dilate = bits, tuple(shape), threshold, dilate
+
+    @property
+    def cells(self):
+        return self.shape[0] * self.shape[1] * self.shape[2]
+
+    def volume(self):
+        """The mask as a bool volume [nx,ny,nz] on the bits' device."""
+        shifts = torch.arange(7, -1, -1, device=self.bits.device, dtype=torch.int32)
+        flat = ((self.bits.to(torch.int32)[:, None] >> shifts) & 1).reshape(-1)[:self.cells]
+        return flat.bool().view(self.shape)
+
+    def fraction(self):
+        """Occupied cells / all cells."""
+        return float(self.volume().sum().item()) / self.cells
+
+
 class NeuTex(nn.Module):
     def __init__(self, opt=None, primitive_type=None, sample_num=None, device='cuda', split_bf16=False, points_per_primitive=None):
         super().__init__()
@@ -326,6 +365,7 @@ class NeuTex(nn.Module):
         self._key = None
         self._inv_handle = None
         self._inv_key = None
+        self._occ = None                     # the occupancy grid (an Occupancy): the user's, not a buffer -- see build_occupancy
         self.to(device)
 
     def layers(self):
@@ -482,15 +522,156 @@ class NeuTex(nn.Module):
         lo, step)`` with ``step = (hi - lo) / (n - 1)`` in float32 (numpy arrays; an ulp longer where the last point would stop short of hi) and ``volume[i,j,k]`` the density at ``lo + (i,j,k) * step``,
         every product and every sum rounded to float32 -- the layout and spacing ``mesh.marching_cubes`` takes.  The kernel generates the
         points; with ``clip`` a lattice that reaches the faces of the cube is 0 there (``query``'s clip), so an iso-surface closes."""
-        dev = self._gpu("evaluates density lattices")
         res, lo32, step = lattice_axes(resolution, lo, hi)
+        return self._lattice(res, lo32, step, clip), lo32, step
+
+    def _lattice(self, res, lo32, step, clip):
+        """ngf_uv_density_lattice on ``res`` points per axis from ``lo32`` in steps of ``step`` (float32 triples) -> the volume on the device."""
+        dev = self._gpu("evaluates density lattices")
         vol = torch.empty(res, device=dev)
         h = self.handle()
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().ngf_uv_density_lattice(h, (C.c_float * 3)(*lo32.tolist()), (C.c_float * 3)(*step.tolist()), res[0], res[1], res[2],
                                                          0 if clip else _lib.UV_QUERY_NO_CLIP, vol.data_ptr(),
                                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return vol, lo32, step
+        return vol
+
+    # --- the occupancy grid: the render skips empty space (include/ngf.h: ngf_uv_occupancy_*, ngf_uv_set_occupancy; DESIGN.md section 4.14) ------
+    @property
+    def occupancy(self):
+        """None when no mask is installed, else the ``Occupancy`` (``shape``, ``bits``, ``threshold``, ``dilate``, ``fraction()``, ``volume()``)."""
+        return self._occ
+
+    @torch.no_grad()
+    def build_occupancy(self, resolution=128, alpha_thres=1e-3, threshold=None, dilate=1):
+        """Build the occupancy grid from the model's own density, install it and return it.  ``resolution``: cells per axis, an int or a triple
+        (1 .. 1024 each).  The density is evaluated on the cells' corners -- ``(n + 1)`` points per axis from -1 in steps of ``float32(2 / n)``,
+        not clipped -- and a cell is occupied iff some cell within Chebyshev distance ``dilate`` (0, 1 or 2) of it has a corner with
+        ``not (sigma <= threshold)``.  With ``threshold=None`` the sigma threshold is ``float32(-log1p(-alpha_thres) / (2 / sample_num))``: the
+        density whose opacity over one nominal segment is ``alpha_thres`` (the fields' ``alphaMask_thres``).  Lattice and reduction run on the device.
+
+        With a mask installed the eval render evaluates a sample only where it is in the cube AND its cell is occupied; every other sample
+        contributes what an out-of-cube sample does (opacity 0, colour 0, zeros in the debug outputs).  The masked frame is therefore, by
+        definition, the reference's frame with sigma set to 0 in empty cells -- NOT the reference's frame, which is why the mask is opt-in.
+        An evaluated sample's density and colour are the same bits as without a mask.
+
+        The mask belongs to the user: it is not rebuilt when a parameter changes (call ``build_occupancy`` again after training), it survives a
+        rebuild of the handle and pickling, and it is no buffer (``state_dict`` does not hold it: ``occupancy_state`` / ``load_occupancy``).
+        ``query``, ``density_lattice``, the texture calls and the differentiable path (``differentiable = True`` with grad enabled) ignore it."""
+        dev = self._gpu("builds occupancy grids")
+        n = _occupancy_shape(resolution)
+        dilate = int(dilate)
+        if not 0 <= dilate <= OCCUPANCY_MAX_DILATE:
+            raise ValueError(f"dilate must be 0 .. {OCCUPANCY_MAX_DILATE}, got {dilate}")
+        if threshold is None:
+            if not 0.0 <= float(alpha_thres) < 1.0:
+                raise ValueError(f"alpha_thres must be in [0, 1), got {alpha_thres!r}")
+            threshold = -np.log1p(-float(alpha_thres)) / (2.0 / self.sample_num)
+        threshold = float(np.float32(threshold))
+        if np.isnan(threshold):
+            raise ValueError("the occupancy threshold is NaN")
+        step = (np.float32(2.0) / np.asarray(n, dtype=np.float32)).astype(np.float32)
+        sigma = self._lattice(tuple(k + 1 for k in n), np.full(3, -1.0, np.float32), step, clip=False)
+        bits = self._occupancy_reduce(sigma, n, threshold, dilate)
+        self._occ = Occupancy(bits, n, threshold, dilate)
+        if self._handle is not None:
+            self._push_occupancy()
+        return self._occ
+
+    def _occupancy_reduce(self, sigma, n, threshold, dilate):
+        """ngf_uv_occupancy_from_lattice: the float32 lattice [(nx+1),(ny+1),(nz+1)] on the device -> the packed bits on the device."""
+        dev = sigma.device
+        L = _lib.lib()
+        bits = torch.empty(((n[0] * n[1] * n[2] + 7) // 8,), dtype=torch.uint8, device=dev)
+        need = int(L.ngf_uv_occupancy_workspace_bytes(n[0], n[1], n[2]))
+        if need < 0:
+            _lib.check(-need)
+        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.ngf_uv_occupancy_from_lattice(sigma.data_ptr(), n[0], n[1], n[2], threshold, dilate, bits.data_ptr(), ws.data_ptr(), need,
+                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            torch.cuda.current_stream().synchronize()          # (the workspace may be freed now)
+        return bits
+
+    def set_occupancy(self, mask):
+        """Install a mask: ``None`` (off), a bool or uint8 volume [nx,ny,nz] (tensor or numpy; non-zero = occupied), or a ``(packed_bits, shape)``
+        pair -- ``np.packbits`` of the C-ordered cells, ``(nx ny nz + 7) // 8`` bytes with the tail bits 0.  See ``build_occupancy`` for what a
+        mask does to the render."""
+        if mask is None:
+            self._occ = None
+        else:
+            if isinstance(mask, tuple) and len(mask) == 2:
+                packed, shape = mask
+                shape = _occupancy_shape(shape)
+                packed = packed.detach().cpu().numpy() if torch.is_tensor(packed) else np.asarray(packed)
+                cells = shape[0] * shape[1] * shape[2]
+                if packed.dtype != np.uint8 or packed.ndim != 1 or packed.shape[0] != (cells + 7) // 8:
+                    raise ValueError(f"the packed bits of a {shape} grid are {(cells + 7) // 8} uint8 values, got {packed.dtype} {packed.shape}")
+                if cells % 8 and int(packed[-1]) & ((1 << (8 - cells % 8)) - 1):
+                    raise ValueError("the tail bits of the last byte must be 0")
+            else:
+                vol = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+                if vol.ndim != 3 or vol.dtype not in (np.bool_, np.uint8):
+                    raise ValueError(f"a mask is a bool or uint8 volume [nx,ny,nz] or a (packed_bits, shape) pair, got {vol.dtype} {vol.shape}")
+                shape = _occupancy_shape(vol.shape)
+                packed = np.packbits(vol.reshape(-1) != 0)
+            self._occ = Occupancy(torch.from_numpy(np.ascontiguousarray(packed)).to(torch.device(self.device)), shape)
+        if self._handle is not None:
+            self._push_occupancy()
+        return self._occ
+
+    def _push_occupancy(self):
+        """The mask -> the handle (beside _push_texture: after every rebuild of the handle, and when the mask changes)."""
+        dev = torch.device(self.device)
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if self._occ is None:
+                _lib.check(_lib.lib().ngf_uv_set_occupancy(self._handle, None, 0, 0, 0, st))
+                return
+            self._occ.bits = self._occ.bits.to(dev).contiguous()
+            n = self._occ.shape
+            _lib.check(_lib.lib().ngf_uv_set_occupancy(self._handle, self._occ.bits.data_ptr(), n[0], n[1], n[2], st))
+            torch.cuda.current_stream().synchronize()          # the library copied the bits
+
+    @torch.no_grad()
+    def occupied(self, xyz):
+        """bool [...] for world points ``xyz`` [..., 3]: the point passes the render's strict in-cube test and its cell's bit is set -- the
+        render kernel's own look-up, cell ``min(int(floor((p + 1) * n / 2)), n - 1)`` per axis in float32."""
+        dev = self._gpu("looks up occupancy")
+        if self._occ is None:
+            raise RuntimeError("no occupancy mask is installed (build_occupancy / set_occupancy)")
+        xyz = torch.as_tensor(xyz)
+        if xyz.shape[-1] != 3:
+            raise ValueError(f"xyz must be [..., 3], got {tuple(xyz.shape)}")
+        lead = tuple(xyz.shape[:-1])
+        pts = xyz.detach().to(dev, torch.float32).reshape(-1, 3).contiguous()
+        out = torch.zeros((pts.shape[0],), dtype=torch.uint8, device=dev)
+        if pts.shape[0]:
+            h = self.handle()
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().ngf_uv_occupancy_lookup(h, pts.data_ptr(), pts.shape[0], out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out.bool().view(lead)
+
+    def occupancy_state(self):
+        """The mask as a dict for a checkpoint, shaped like the fields' ``alphaMask.*`` keys: ``'occupancy.shape'`` (3 ints) and
+        ``'occupancy.mask'`` (``np.packbits`` of the cells); empty without a mask.  Not buffers: ``state_dict`` is unchanged."""
+        if self._occ is None:
+            return {}
+        return {'occupancy.shape': np.asarray(self._occ.shape, np.int64), 'occupancy.mask': self._occ.bits.detach().cpu().numpy().copy()}
+
+    def load_occupancy(self, state):
+        """Install the mask of an ``occupancy_state()`` dict (a dict without the keys switches the mask off)."""
+        has = [k in state for k in ('occupancy.shape', 'occupancy.mask')]
+        if not any(has):
+            return self.set_occupancy(None)
+        if not all(has):
+            raise ValueError("an occupancy state holds both 'occupancy.shape' and 'occupancy.mask'")
+        shape = np.asarray(state['occupancy.shape']).reshape(-1)
+        if shape.shape[0] != 3:
+            raise ValueError(f"'occupancy.shape' holds three cell counts, got {shape.tolist()}")
+        mask = state['occupancy.mask']
+        mask = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+        return self.set_occupancy((mask.reshape(-1), tuple(int(s) for s in shape)))
 
     @torch.no_grad()
     def export_mesh(self, path=None, *, level, resolution=256, viewdir=None, texture_resolution=512, normals=False, flip=False):
@@ -590,8 +771,15 @@ class NeuTex(nn.Module):
             self._write_atlas_obj(path, verts, faces, st, viewdir, texture_resolution)
         return verts, faces, colors, st
 
+    def __getstate__(self):              # handles and engines are not state: not pickled, not deep-copied; the occupancy mask is (its bits are a tensor)
+        d = self.__dict__.copy()
+        for k in ('_handle', '_key', '_inv_handle', '_inv_key', '_uv_engine'):
+            d[k] = None
+        return d
+
     def __setstate__(self, state):
         super().__setstate__(state)
+        self.__dict__.setdefault('_occ', None)
         self.net_texture._owner = weakref.ref(self)
 
     def release(self):
@@ -636,6 +824,8 @@ class NeuTex(nn.Module):
             _lib.lib().ngf_uv_destroy(self._handle)
         self._handle, self._key = out, key
         self._push_texture()
+        if self._occ is not None:
+            self._push_occupancy()
         return out
 
     # --- training (uv_train.py) ---------------------------------------------------------------------------------------------------
@@ -681,7 +871,9 @@ class NeuTex(nn.Module):
     def forward(self, camera_position=None, ray_direction=None, background_color=None, jitter_u=None, debug=False, collect_stats=False,
                 template_points=None):
         """model.py:27: camera_position [N,3], ray_direction [N,R,3] (normalised), background_color [N,3] or None.  With ``differentiable`` set
-        and grad enabled: the training dict (color, transmittance, points, points_original, points_inverse_weights, uv, lazy points_inverse)."""
+        and grad enabled: the training dict (color, transmittance, points, points_original, points_inverse_weights, uv, lazy points_inverse).
+        With an occupancy mask installed (``build_occupancy``) the eval path skips the samples of empty cells: the frame is the reference's with
+        sigma set to 0 there, and ``collect_stats`` counts the samples evaluated and the passes run.  The differentiable path ignores the mask."""
         if self.differentiable and torch.is_grad_enabled():
             if debug or collect_stats:
                 raise ValueError("debug / collect_stats belong to the eval path (torch.no_grad() or differentiable = False)")
