@@ -518,8 +518,9 @@ int ngf_uv_density_lattice(const ngf_uv *m, const float lo[3], const float step[
  * ngf_uv_occupancy_lookup: out[i] = 1 if xyz[i] (DEVICE [n,3]) is occupied in the handle's mask, else 0 -- the render's own look-up function.
  * NGF_E_ARG, before any GPU work: null pointers, an axis outside 1 .. 1024, dilate outside 0 .. 2, a NaN threshold, a workspace that is too small,
  * n < 0, a look-up on a handle without a mask.  n == 0 returns NGF_OK without a launch.
- * The mask is the RENDER's alone: ngf_uv_query, ngf_uv_density_lattice, the texture calls (ngf_uv_texture_eval, ngf_uv_texture_edit) and the
- * trainer (ngf_uv_train_*) do not consult it. */
+ * The handle's mask is the RENDER's alone: ngf_uv_query, ngf_uv_density_lattice and the texture calls (ngf_uv_texture_eval, ngf_uv_texture_edit)
+ * do not consult it.  The trainer (ngf_uv_train_*) never reads a render handle's mask either; it takes a copy of its own, opt-in, through
+ * ngf_uv_trainer_set_occupancy (below), and without one it evaluates every in-cube sample. */
 int64_t ngf_uv_occupancy_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int ngf_uv_occupancy_from_lattice(const float *sigma, int32_t nx, int32_t ny, int32_t nz, float threshold, int32_t dilate, uint8_t *bits,
                                   void *workspace, int64_t workspace_bytes, void *hip_stream);
@@ -665,6 +666,21 @@ int ngf_uv_train_backward(ngf_uv_trainer *t, int64_t ticket, const float *d_colo
 int ngf_uv_train_get_grads(ngf_uv_trainer *t, float *const out[NGF_UV_TRAIN_PARAMS], void *hip_stream);
 /* after writing to a parameter's memory: kept for the trainers' common contract; the UV trainer packs nothing and reads the weights in place */
 int ngf_uv_train_params_changed(ngf_uv_trainer *t);
+/* Training through the occupancy grid (additive, ABI 5; OPT-IN -- grid, bit order and look-up as above).  With a mask in the trainer a sample is
+ * valid iff it passes the strict in-cube test AND its cell's bit is set, decided on the float32 position the forward writes to ray_pos: the
+ * decision of the eval render on the same batch.  A sample that is not valid is what an out-of-cube sample is: the geometry and texture networks
+ * do not evaluate it, its sigma is 0, its opacity 0 and its blend weight exactly 0, and it contributes no gradient to those networks.  The gauge
+ * network still runs on every sample: the bits of `uv` do not depend on the mask.  Without a mask every launch is the kernel it was before.
+ * ngf_uv_trainer_set_occupancy: copies the bits (DEVICE) into a buffer the trainer owns, as ngf_uv_set_occupancy does for a render handle;
+ *   bits_dev = NULL switches the mask off.  It waits for the device when it replaces or drops a mask.  The forwards after the call use it; the
+ *   backward of an earlier forward is unaffected (it reads that forward's sample list, never the mask).
+ * ngf_uv_train_counts: out[0] = the in-cube samples of the last forward, out[1] = those it evaluated (the kept ones); equal without a mask.
+ *   Summed on the device from per-ray integer counts.  Synchronises the stream.
+ * ngf_uv_train_kept: out_dev [n_cams * rays_per_cam * n_samples] (DEVICE) = 1 where the last forward evaluated the sample, else 0.
+ * NGF_E_ARG, before any GPU work: a null handle or pointer, an axis outside 1 .. 1024 (with bits_dev set), counts / kept before any forward. */
+int ngf_uv_trainer_set_occupancy(ngf_uv_trainer *t, const uint8_t *bits_dev, int32_t nx, int32_t ny, int32_t nz, void *hip_stream);
+int ngf_uv_train_counts(ngf_uv_trainer *t, int64_t out[2], void *hip_stream);
+int ngf_uv_train_kept(ngf_uv_trainer *t, uint8_t *out_dev, void *hip_stream);
 /* test aid: ONE layer-sized GEMM of the trainer on caller-owned DEVICE buffers, through the launch code the trainer's layers go through (strides,
  * grid sizes and the chunk count are the trainer's own), so that a test can compare it with fp64 at the row counts a batch never pins down.
  * The layer is W [out, in]; `rows` sizes the launch, and with rows_dev set only min(rows, *rows_dev) rows are computed (the in-cube count).

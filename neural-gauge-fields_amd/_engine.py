@@ -110,11 +110,13 @@ def release_engine(model, attr):
         setattr(model, attr, None)
 
 
-def replay(model, attr, engine, first, ticket, saved, inputs, d, want, whose="field"):
+def replay(model, attr, engine, first, ticket, saved, inputs, d, want, whose="field", before_rerender=None):
     """The gradients of one autograd node: ``first`` / ``ticket`` are the engine and ticket of its forward, ``saved`` the parameter tensors it saw,
     ``inputs`` the arguments of ``forward``, ``d`` the incoming gradients of ``backward``.  The engine is the model's CURRENT one: that of the
     forward (the common case: its identity is the whole check), unless a larger batch or a re-allocation had it rebuilt in between (``engine()``
-    gets it).  After another forward through the engine (a stale ticket), or on a new engine, the batch is rendered again, then its backward."""
+    gets it).  After another forward through the engine (a stale ticket), or on a new engine, the batch is rendered again, then its backward;
+    ``before_rerender(eng)`` is called first then: the place to refuse when the engine no longer holds the state the forward ran with
+    (uv_train.py: the occupancy mask)."""
     eng = first
     if getattr(model, attr, None) is not eng or eng._h is None:
         eng = engine()
@@ -122,6 +124,8 @@ def replay(model, attr, engine, first, ticket, saved, inputs, d, want, whose="fi
         raise RuntimeError(f"the {whose}'s parameter tensors were re-allocated between forward and backward")
     grads = eng.backward(ticket, *d, want) if eng is first else None
     if grads is None:
+        if before_rerender is not None:
+            before_rerender(eng)
         *_, ticket = eng.forward(*inputs)
         grads = eng.backward(ticket, *d, want)
         if grads is None:

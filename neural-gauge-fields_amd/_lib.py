@@ -31,6 +31,7 @@ SYMBOLS = ["ngf_field_create", "ngf_field_destroy", "ngf_field_render", "ngf_fie
            "ngf_infoinv_train_adam_ext",
            "ngf_uv_trainer_create", "ngf_uv_trainer_destroy", "ngf_uv_trainer_bytes", "ngf_sizeof_uv_train_desc", "ngf_uv_train_forward",
            "ngf_uv_train_backward", "ngf_uv_train_get_grads", "ngf_uv_train_params_changed", "ngf_uv_texture_eval", "ngf_debug_uvt_gemm",
+           "ngf_uv_trainer_set_occupancy", "ngf_uv_train_counts", "ngf_uv_train_kept",
            "ngf_debug_ii_product", "ngf_debug_ii_counts",
            "ngf_mesh_workspace_bytes", "ngf_mesh_count", "ngf_mesh_emit", "ngf_debug_mesh_scan",
            "ngf_field_query", "ngf_uv_query", "ngf_uv_density_lattice",

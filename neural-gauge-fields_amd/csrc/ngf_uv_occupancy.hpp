@@ -1,6 +1,7 @@
 // ngf_uv_occupancy.hpp -- the occupancy grid of a NeuTex handle: nx x ny x nz cells over the cube [-1,1]^3, one bit per cell (1 = occupied), cell
 // (cx,cy,cz) at linear index (cx ny + cy) nz + cz (the C order of ngf_uv_density_lattice), packed like np.packbits -- most significant bit first,
-// as ngf_pack_mask_bits packs.  The ONE look-up the render kernel (ngf_uv.hpp, OCC instantiations) and ngf_uv_occupancy_lookup share.
+// as ngf_pack_mask_bits packs.  The ONE look-up the render kernel (ngf_uv.hpp, OCC instantiations), ngf_uv_occupancy_lookup and the trainer
+// (ngf_uv_train.hpp, the OCC forms of uvt_rays_kernel and uvt_compact_kernel) share.
 //
 // Nearest cell, not the fields' trilinear alpha test: a sample asks one bit, so that "occupied" is a property of a cell a test can restate and a
 // dilated mask is conservative by construction.

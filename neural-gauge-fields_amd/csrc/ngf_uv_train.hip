@@ -62,6 +62,11 @@ struct ngf_uv_trainer {
     int32_t S = 0;
     int64_t ticket = 0, next_ticket = 0;
     bool have_grads = false;
+    // the occupancy mask (ngf_uv_trainer_set_occupancy): an owned copy of the bits, outside `mem` (it is replaced while the handle lives)
+    uint8_t *occ = nullptr;
+    int32_t occ_n[3] = {0, 0, 0};
+    int32_t *cnt_in = nullptr, *off_in = nullptr, *total_in = nullptr;      // in-cube samples per ray, their scan and sum (written with a mask only)
+    bool fwd_occ = false;                    // the last forward ran with a mask: total_in holds its in-cube count (else `total` is both counts)
 };
 
 namespace {
@@ -191,6 +196,7 @@ int ngf_uv_trainer_destroy(ngf_uv_trainer *t)
     {
         DeviceScope ds(t->device);
         t->mem.free_all();
+        if (t->occ) (void)hipFree(t->occ);
     }
     delete t;
     return NGF_OK;
@@ -222,6 +228,7 @@ int ngf_uv_trainer_create(const ngf_uv_train_desc *desc, ngf_uv_trainer **out, v
     auto I = [&](int32_t **p, int64_t n) { if (!rc) rc = t->mem.alloc(p, (size_t)n); };
     F(&t->seg, cap); F(&t->opac, cap); F(&t->acct, cap); F(&t->xraw, d.max_rays * 4); F(&t->uv, cap * 3);
     I(&t->cnt, d.max_rays); I(&t->off, d.max_rays); I(&t->total, 1); I(&t->list, cap); I(&t->vid, cap);
+    I(&t->cnt_in, d.max_rays); I(&t->off_in, d.max_rays); I(&t->total_in, 1);
     F(&t->Xga, cap * 64); F(&t->Xg, cap * 64); F(&t->Xt, cap * 64); F(&t->X2, cap * 296);
     for (int l = 0; l < L; ++l) {
         const int o = t->shape[l].out;
@@ -260,6 +267,54 @@ int ngf_uv_train_params_changed(ngf_uv_trainer *t)
     return NGF_OK;          // the weights are read in place at every launch: nothing is packed
 }
 
+// the contract of ngf_uv_set_occupancy (ngf_uv.hip) on the trainer's own copy.  The forwards after this call read the new bits; the backward of a
+// forward before it reads that forward's list and vid, never the mask.
+int ngf_uv_trainer_set_occupancy(ngf_uv_trainer *t, const uint8_t *bits_dev, int32_t nx, int32_t ny, int32_t nz, void *hip_stream)
+{
+    if (!t) return fail(NGF_E_ARG, "ngf_uv_trainer_set_occupancy: null handle");
+    if (bits_dev && (nx < 1 || ny < 1 || nz < 1 || nx > kUvOccMaxAxis || ny > kUvOccMaxAxis || nz > kUvOccMaxAxis))
+        return fail(NGF_E_ARG, "ngf_uv_trainer_set_occupancy: a grid of %d x %d x %d cells (every axis needs 1 .. %d)", nx, ny, nz, kUvOccMaxAxis);
+    DeviceScope ds(t->device);
+    uint8_t *fresh = nullptr;
+    if (bits_dev) {
+        const size_t nbytes = ((size_t)nx * ny * nz + 7) / 8;
+        HIP_TRY(hipMalloc((void **)&fresh, nbytes));
+        if (hipMemcpyAsync(fresh, bits_dev, nbytes, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream) != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(NGF_E_HIP, "ngf_uv_trainer_set_occupancy: copying the bits failed");
+        }
+    }
+    if (t->occ) (void)hipFree(t->occ);          // (waits for the device's work: no launch still reads the old bits)
+    t->occ = fresh;
+    t->occ_n[0] = fresh ? nx : 0; t->occ_n[1] = fresh ? ny : 0; t->occ_n[2] = fresh ? nz : 0;
+    return NGF_OK;
+}
+
+int ngf_uv_train_counts(ngf_uv_trainer *t, int64_t out[2], void *hip_stream)
+{
+    if (!t || !out) return fail(NGF_E_ARG, "ngf_uv_train_counts: null argument");
+    if (t->ticket <= 0) return fail(NGF_E_ARG, "ngf_uv_train_counts: the trainer has run no forward");
+    DeviceScope ds(t->device);
+    hipStream_t st = (hipStream_t)hip_stream;
+    int32_t kept = 0, in_cube = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, t->total, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (t->fwd_occ) HIP_TRY(hipMemcpyAsync(&in_cube, t->total_in, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out[0] = t->fwd_occ ? in_cube : kept;
+    out[1] = kept;
+    return NGF_OK;
+}
+
+int ngf_uv_train_kept(ngf_uv_trainer *t, uint8_t *out_dev, void *hip_stream)
+{
+    if (!t || !out_dev) return fail(NGF_E_ARG, "ngf_uv_train_kept: null argument");
+    if (t->ticket <= 0) return fail(NGF_E_ARG, "ngf_uv_train_kept: the trainer has run no forward");
+    DeviceScope ds(t->device);
+    const int64_t M = t->nrays * t->S;
+    NGF_LAUNCH(uvt_kept_kernel, dim3(blocks(M)), dim3(256), 0, (hipStream_t)hip_stream, (const int32_t *)t->vid, M, out_dev);
+    return NGF_OK;
+}
+
 int ngf_uv_train_forward(ngf_uv_trainer *t, const float *campos, const float *raydir, const float *bg, const float *jitter_u, int32_t n_cams,
                          int64_t rays_per_cam, int32_t n_samples, float *color, float *trans, float *uv, float *weight, float *ray_pos, int64_t *ticket,
                          void *hip_stream)
@@ -277,14 +332,30 @@ int ngf_uv_train_forward(ngf_uv_trainer *t, const float *campos, const float *ra
     const int64_t M = nrays * S;
     const int D = t->desc.sphere ? 3 : 2;
     t->have_grads = false;
+    // which samples are valid: in-cube, and with a mask in an occupied cell.  Without a mask the launches are the kernels without the look-up.
+    UvtOcc O{};
+    const bool occ = t->occ != nullptr;
+    if (occ) {
+        O.bits = t->occ; O.cnt_in = t->cnt_in;
+        for (int k = 0; k < 3; ++k) { O.n[k] = t->occ_n[k]; O.h[k] = (float)t->occ_n[k] * 0.5f; }
+    }
     {
         UvtRays A{};
         A.cam = campos; A.raydir = raydir; A.U = jitter_u; A.ray_pos = ray_pos; A.seg = t->seg; A.cnt = t->cnt;
         A.nrays = nrays; A.R = (int32_t)rays_per_cam; A.S = S;
-        NGF_LAUNCH(uvt_rays_kernel, dim3(blocks(nrays)), dim3(256), 0, st, A);
+        if (occ) NGF_LAUNCH((uvt_rays_kernel<true>), dim3(blocks(nrays)), dim3(256), 0, st, A, O);
+        else NGF_LAUNCH((uvt_rays_kernel<false>), dim3(blocks(nrays)), dim3(256), 0, st, A, O);
     }
     NGF_LAUNCH(uvt_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)t->cnt, nrays, t->off, t->total);
-    NGF_LAUNCH(uvt_compact_kernel, dim3(blocks(nrays)), dim3(256), 0, st, (const float *)ray_pos, (const int32_t *)t->off, nrays, S, t->list, t->vid);
+    if (occ) {
+        NGF_LAUNCH(uvt_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t *)t->cnt_in, nrays, t->off_in, t->total_in);
+        NGF_LAUNCH((uvt_compact_kernel<true>), dim3(blocks(nrays)), dim3(256), 0, st, (const float *)ray_pos, (const int32_t *)t->off, nrays, S, t->list,
+                   t->vid, O);
+    } else {
+        NGF_LAUNCH((uvt_compact_kernel<false>), dim3(blocks(nrays)), dim3(256), 0, st, (const float *)ray_pos, (const int32_t *)t->off, nrays, S, t->list,
+                   t->vid, O);
+    }
+    t->fwd_occ = occ;
     NGF_LAUNCH(uvt_pe_pos_kernel, dim3(blocks(M)), dim3(256), 0, st, (const float *)ray_pos, M, t->Xga);
     int rc = NGF_OK;
     // gauge network on every sample -> uv

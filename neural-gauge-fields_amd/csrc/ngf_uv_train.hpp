@@ -5,11 +5,13 @@
 // 64 x 64 block tile, four waves of 32 x 32) with a fused epilogue: bias + activation in the forward, "+ second gradient, x activation
 // derivative" in the backward.  The gauge network runs on every sample (uv is an output); the geometry and texture networks run on the
 // compacted list of in-cube samples only (their opacity is exactly 0 otherwise, renderer.py:222), whose length stays on the device: those
-// launches are sized for the whole batch and their surplus blocks return at once.  Every layer's POST-activation output is kept; for ReLU
+// launches are sized for the whole batch and their surplus blocks return at once.  With an occupancy mask in the trainer (UvtOcc) the list holds
+// the in-cube samples of occupied cells only; everything behind the list is the same code.  Every layer's POST-activation output is kept; for ReLU
 // and LeakyReLU(0.2) its sign is the derivative torch uses.  Weight gradients are dZ^T . X over fixed 1024-row chunks, summed in chunk
 // order by a second kernel: no float atomics, two backwards of one batch are bit-identical.
 #pragma once
 #include "ngf_device.hpp"
+#include "ngf_uv_occupancy.hpp"
 
 namespace ngf {
 
@@ -177,12 +179,37 @@ struct UvtRays {
     const float *U;        // [N,R,S]
     float *ray_pos;        // [N,R,S,3] (output)
     float *seg;            // [N R S]
-    int32_t *cnt;          // [N R] in-cube samples per ray
+    int32_t *cnt;          // [N R] valid samples per ray: the in-cube ones, with a mask (OCC) those of them whose cell is occupied
     int64_t nrays;
     int32_t R, S;
 };
 
-__global__ void __launch_bounds__(256) uvt_rays_kernel(const UvtRays A)
+// The trainer's occupancy mask (ngf_uv_trainer_set_occupancy; grid and bit order of ngf_uv_occupancy.hpp), read by the OCC instantiations of
+// uvt_rays_kernel and uvt_compact_kernel alone.  Both decide a sample by the SAME expression on the SAME floats -- the strict in-cube test, then
+// uv_occ_lookup, on the float32 position the rays kernel stores in ray_pos and the compact kernel reads back -- so the count and the list agree.
+struct UvtOcc {
+    const uint8_t *bits;
+    int32_t n[3];
+    float h[3];            // (float)n[k] * 0.5f
+    int32_t *cnt_in;       // [N R] in-cube samples per ray (rays kernel, OCC only)
+};
+
+// p [3] is valid: strictly inside the cube and, with a mask, in an occupied cell (only lanes that passed the in-cube test load a byte)
+template <bool OCC>
+__device__ __forceinline__ bool uvt_valid(const UvtOcc &O, const float p[3], bool &in_cube)
+{
+    bool valid = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) valid = valid && (p[k] > -1.0f) && (p[k] < 1.0f);
+    in_cube = valid;
+    if constexpr (OCC) {
+        if (valid) valid = uv_occ_lookup(O.bits, O.n, O.h, p);
+    }
+    return valid;
+}
+
+template <bool OCC>
+__global__ void __launch_bounds__(256) uvt_rays_kernel(const UvtRays A, const UvtOcc O)
 {
     const int64_t ray = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (ray >= A.nrays) return;
@@ -199,7 +226,7 @@ __global__ void __launch_bounds__(256) uvt_rays_kernel(const UvtRays A)
     const float t0 = fmaxf((tmin < tmax) ? tmin : 0.0f, 0.0f);
     const float dt = (float)(2.0 / S), dtj = (float)((2.0 / S) * 0.05);
     double cum = 0.0;
-    int n = 0;
+    int n = 0, n_in = 0;
     for (int s = 0; s < S; ++s) {
         const int64_t m = ray * S + s;
         const float sg = dt + dtj * (A.U[m] - 0.5f);
@@ -207,17 +234,20 @@ __global__ void __launch_bounds__(256) uvt_rays_kernel(const UvtRays A)
         cum += (double)sg;
         const float e0 = t0 + (float)before, e1 = t0 + (float)cum;
         const float mid = (e0 + e1) / 2.0f;
-        bool valid = true;
+        float p[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-            const float p = cp[k] + d[k] * mid;
-            A.ray_pos[m * 3 + k] = p;
-            valid = valid && (p > -1.0f) && (p < 1.0f);
+        for (int k = 0; k < 3; ++k) {
+            p[k] = cp[k] + d[k] * mid;
+            A.ray_pos[m * 3 + k] = p[k];
         }
+        bool in_cube;
+        const bool valid = uvt_valid<OCC>(O, p, in_cube);
         A.seg[m] = sg;
         n += valid ? 1 : 0;
+        n_in += in_cube ? 1 : 0;
     }
     A.cnt[ray] = n;
+    if constexpr (OCC) O.cnt_in[ray] = n_in;
 }
 
 // exclusive scan of cnt [n] -> off [n], total -> *total (one block of 1024)
@@ -228,23 +258,29 @@ __global__ void __launch_bounds__(1024) uvt_scan_kernel(const int32_t *cnt, int6
     if (threadIdx.x == 1023) *total = sum;
 }
 
-// list[v] = flat sample index of in-cube sample v (ray-major, sample order); vid[m] = v or -1
-__global__ void __launch_bounds__(256) uvt_compact_kernel(const float *ray_pos, const int32_t *off, int64_t nrays, int S, int32_t *list, int32_t *vid)
+// list[v] = flat sample index of valid sample v (ray-major, sample order); vid[m] = v or -1.  Valid as uvt_rays_kernel<OCC> counted it.
+template <bool OCC>
+__global__ void __launch_bounds__(256) uvt_compact_kernel(const float *ray_pos, const int32_t *off, int64_t nrays, int S, int32_t *list, int32_t *vid,
+                                                          const UvtOcc O)
 {
     const int64_t ray = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (ray >= nrays) return;
     int32_t v = off[ray];
     for (int s = 0; s < S; ++s) {
         const int64_t m = ray * S + s;
-        bool valid = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-            const float p = ray_pos[m * 3 + k];
-            valid = valid && (p > -1.0f) && (p < 1.0f);
-        }
+        const float p[3] = {ray_pos[m * 3], ray_pos[m * 3 + 1], ray_pos[m * 3 + 2]};
+        bool in_cube;
+        const bool valid = uvt_valid<OCC>(O, p, in_cube);
         if (valid) list[v] = (int32_t)m;
         vid[m] = valid ? v++ : -1;
     }
+}
+
+// kept[m] = 1 where sample m is in the list of the last forward (ngf_uv_train_kept)
+__global__ void __launch_bounds__(256) uvt_kept_kernel(const int32_t *vid, int64_t M, uint8_t *kept)
+{
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m < M) kept[m] = vid[m] >= 0 ? 1 : 0;
 }
 
 // [x (D), sin(x_d 2^f) d-major (D F), cos(same) (D F), zeros up to ld] (util.py:427-438)

@@ -66,6 +66,9 @@ def _bind(L):
     L.ngf_uv_train_backward.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ngf_uv_train_get_grads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.ngf_uv_train_params_changed.argtypes = [C.c_void_p]
+    L.ngf_uv_trainer_set_occupancy.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    L.ngf_uv_train_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+    L.ngf_uv_train_kept.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     if L.ngf_sizeof_uv_train_desc() != C.sizeof(UvTrainDesc):
         raise RuntimeError("libngf_hip.so ABI mismatch (ngf_uv_train_desc layout)")
     L._ngf_uv_train_bound = True
@@ -109,15 +112,50 @@ class UvGrad(GradEngine):
             _lib.check(self.L.ngf_uv_trainer_create(C.byref(d), C.byref(out), st))
         self._h = out
         self.key = self._key(params)
+        self.occupancy = None       # the uvmapping.Occupancy whose bits the trainer holds a copy of (set_occupancy), or None
+        self._shape = None          # (N, R, S) of the last forward
 
     @staticmethod
     def _key(params):
         return tuple((p.data_ptr(), tuple(p.shape)) for p in params)
 
+    def set_occupancy(self, occ):
+        """Train through the mask ``occ`` (a uvmapping.Occupancy; None = off) from the next forward on: only the in-cube samples of occupied
+        cells are evaluated (include/ngf.h: ngf_uv_trainer_set_occupancy).  The library copies the bits; an object that is already the
+        engine's is not pushed again."""
+        if occ is self.occupancy:
+            return
+        with on_stream(self.dev) as st:
+            if occ is None:
+                _lib.check(self.L.ngf_uv_trainer_set_occupancy(self._h, None, 0, 0, 0, st))
+            else:
+                bits = occ.bits.to(self.dev).contiguous()
+                n = occ.shape
+                _lib.check(self.L.ngf_uv_trainer_set_occupancy(self._h, bits.data_ptr(), n[0], n[1], n[2], st))
+                torch.cuda.current_stream(self.dev).synchronize()          # (still inside on_stream: the stream the copy went to) `bits` may go now
+        self.occupancy = occ
+
+    def counts(self):
+        """``(in_cube, kept)`` of the last forward: its in-cube samples and those of them it evaluated (equal without a mask).  Synchronises."""
+        out = (C.c_int64 * 2)()
+        with on_stream(self.dev) as st:
+            _lib.check(self.L.ngf_uv_train_counts(self._h, out, st))
+        return int(out[0]), int(out[1])
+
+    def kept_mask(self):
+        """bool [N,R,S]: the samples the last forward evaluated."""
+        if self._shape is None:
+            raise RuntimeError("the engine has run no forward")
+        out = torch.empty(self._shape, dtype=torch.uint8, device=self.dev)
+        with on_stream(self.dev) as st:
+            _lib.check(self.L.ngf_uv_train_kept(self._h, out.data_ptr(), st))
+        return out.bool()
+
     def forward(self, cam, rd, bg, U):
         """-> (color [N,R,3], trans [N,R], uv [N,R,S,D], weight [N,R,S], ray_pos [N,R,S,3], ticket)."""
         self.sync()
         N, R, S = U.shape
+        self._shape = (N, R, S)
         D = 2 if self.net.primitive_type == 'square' else 3
         f = dict(device=self.dev, dtype=torch.float32)
         color, trans = torch.empty((N, R, 3), **f), torch.empty((N, R), **f)
@@ -149,6 +187,7 @@ class _UvRender(torch.autograd.Function):
     def forward(ctx, net, eng, cam, rd, bg, U, *params):
         color, trans, uv, weight, pos, ticket = eng.forward(cam, rd, bg, U)
         ctx.net, ctx.engine, ctx.ticket = net, eng, ticket
+        ctx.occupancy = getattr(eng, "occupancy", None)          # the mask this forward trained through (the Occupancy object, or None)
         ctx.has_bg = bg is not None
         ctx.save_for_backward(cam, rd, U, *(() if bg is None else (bg,)), *params)
         ctx.mark_non_differentiable(pos)
@@ -164,8 +203,15 @@ class _UvRender(torch.autograd.Function):
         f = dict(device=U.device, dtype=torch.float32)      # the library reads d color and d transmittance unconditionally
         dc = torch.zeros((N, R, 3), **f) if d_color is None else _f32(d_color)
         dt = torch.zeros((N, R), **f) if d_trans is None else _f32(d_trans)
+
+        def same_mask(eng):          # before the batch is rendered again: through the mask of the forward, or not at all
+            if getattr(eng, "occupancy", None) is not ctx.occupancy:
+                raise RuntimeError("the occupancy mask this forward trained through is no longer the one in the training engine (another forward "
+                                   "ran after the mask was changed): its backward would render the batch again through a different mask and "
+                                   "differentiate a different function.  Call backward before the next forward, or keep the mask until then")
+
         grads = replay(ctx.net, '_uv_engine', lambda: ctx.net._uv_grad_engine(N * R, S), ctx.engine, ctx.ticket, params, (cam, rd, bg, U),
-                       (dc, dt, _f32(d_uv), _f32(d_weight)), [bool(w) for w in ctx.needs_input_grad[6:]], whose="model")
+                       (dc, dt, _f32(d_uv), _f32(d_weight)), [bool(w) for w in ctx.needs_input_grad[6:]], whose="model", before_rerender=same_mask)
         return (None,) * 6 + tuple(grads)
 
 

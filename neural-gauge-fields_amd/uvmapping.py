@@ -32,6 +32,8 @@ ngf_uv_inverse_trainer_*); otherwise they are plain torc
 
 Training: with ``net.differentiable = True`` (an attribute, never saved) and grad enabled, ``forward`` returns the reference's training dict
 with a graph over every parameter (uv_train.py, include/ngf.h: ngf_uv_trainer_*).  Off, or under ``torch.no_grad()``, it is the eval path.
+With ``net.occupancy_in_training = True`` as well (an attribute, never saved) it trains through the installed occupancy mask: empty cells are
+neither evaluated nor given a gradient (include/ngf.h: ngf_uv_trainer_set_occupancy).
 """
 from __future__ import annotations
 
@@ -557,7 +559,15 @@ class NeuTex(nn.Module):
 
         The mask belongs to the user: it is not rebuilt when a parameter changes (call ``build_occupancy`` again after training), it survives a
         rebuild of the handle and pickling, and it is no buffer (``state_dict`` does not hold it: ``occupancy_state`` / ``load_occupancy``).
-        ``query``, ``density_lattice``, the texture calls and the differentiable path (``differentiable = True`` with grad enabled) ignore it."""
+        ``query``, ``density_lattice`` and the texture calls ignore it, and so does the differentiable path (``differentiable = True`` with grad
+        enabled) unless ``occupancy_in_training`` is set.
+
+        Training through the mask (``net.occupancy_in_training = True``, off by default): the differentiable forward
+        then evaluates the geometry and texture networks only on the in-cube samples of occupied cells -- the eval render's decision on the same
+        batch -- and every other sample has sigma 0, blend weight exactly 0 and no gradient into those networks (the gauge network still runs
+        on every sample: ``uv`` does not depend on the mask).  The mask is still never rebuilt behind the user's back.  A cell masked empty
+        gets no gradient, so its density cannot rise again by training alone: build the mask after a warm-up, and rebuild it every so often.
+        ``build_occupancy`` evaluates the WHOLE lattice, masked cells included, so cells can come back."""
         dev = self._gpu("builds occupancy grids")
         n = _occupancy_shape(resolution)
         dilate = int(dilate)
@@ -775,6 +785,7 @@ class NeuTex(nn.Module):
         d = self.__dict__.copy()
         for k in ('_handle', '_key', '_inv_handle', '_inv_key', '_uv_engine'):
             d[k] = None
+        d.pop('occupancy_in_training', None)          # a training switch, not state
         return d
 
     def __setstate__(self, state):
@@ -829,9 +840,16 @@ class NeuTex(nn.Module):
         return out
 
     # --- training (uv_train.py) ---------------------------------------------------------------------------------------------------
+    occupancy_in_training = False          # train through the installed occupancy mask: a plain attribute like
+                                           # ``differentiable`` -- never saved, not in state_dict, not pickled
+
     def _uv_grad_engine(self, nrays, S):
+        """The training engine for this batch shape, holding the mask training goes through: ``occupancy`` with ``occupancy_in_training`` set,
+        else none.  The engine is told only when that object changed since it was last told; a rebuilt engine is told again."""
         from .uv_train import UvGrad, train_params
-        return _engine.grad_engine(self, '_uv_engine', UvGrad, train_params(self), nrays, S)
+        eng = _engine.grad_engine(self, '_uv_engine', UvGrad, train_params(self), nrays, S)
+        eng.set_occupancy(self._occ if self.occupancy_in_training else None)
+        return eng
 
     @property
     def grad_engine(self):
@@ -873,7 +891,11 @@ class NeuTex(nn.Module):
         """model.py:27: camera_position [N,3], ray_direction [N,R,3] (normalised), background_color [N,3] or None.  With ``differentiable`` set
         and grad enabled: the training dict (color, transmittance, points, points_original, points_inverse_weights, uv, lazy points_inverse).
         With an occupancy mask installed (``build_occupancy``) the eval path skips the samples of empty cells: the frame is the reference's with
-        sigma set to 0 there, and ``collect_stats`` counts the samples evaluated and the passes run.  The differentiable path ignores the mask."""
+        sigma set to 0 there, and ``collect_stats`` counts the samples evaluated and the passes run.  The differentiable path ignores the mask
+        unless ``occupancy_in_training`` is set; then it trains through the installed mask as it stands -- the same samples the eval path would
+        evaluate, no gradient for a cell masked empty -- and never rebuilds it: ``build_occupancy`` after a warm-up and again every so often
+        (it evaluates the whole lattice, so cells can come back).  ``grad_engine.counts()`` / ``grad_engine.kept_mask()`` tell what the last
+        forward kept.  A backward that has to render its batch again (another forward ran in between) after the mask was changed raises."""
         if self.differentiable and torch.is_grad_enabled():
             if debug or collect_stats:
                 raise ValueError("debug / collect_stats belong to the eval path (torch.no_grad() or differentiable = False)")
